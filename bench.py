@@ -1,21 +1,25 @@
 #!/usr/bin/env python3
-"""Headline benchmark: Mvoxel-smooths/s at 512^3 fp32 (BASELINE.json metric),
-plus V-cycles/s, HBM roofline fraction of the smoother kernel and the CPU
-baseline (the fp64 oracle, 1 thread, bounded sample).
+"""Headline benchmark: Mvoxel-smooths/s at 512^3 fp32 (BASELINE.json metric) and
+the HBM roofline fraction of the smoother kernel in the timed steps; with --full
+also V-cycles/s, the sustained window, the per-cycle cost of the precisions and
+the CPU baseline (the fp64 oracle, 1 thread, bounded sample).
 
 Workload (config C4 of BASELINE.json, the largest single-GPU config the metric
 is quoted on): 512^3 fp32 image, VED-form full 3x3 diffusion tensor (synthetic,
 generated on the device), dt 0.1, unit spacing, 4-colour Gauss-Seidel smoother.
 One step = one level-0 smoother sweep (all colours) over the whole volume.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, settles, warms up, times the K steps, writes the iterate the
+last step left (--dump-outputs) and prints the line; everything else the line can
+carry is measured only with --full.
 bench.py itself starts no processes: for N > 1 it must run under
 torch.distributed.run with one process per GPU (WORLD_SIZE = N; --gpus must
 match it, or the run exits with an error).  The volume is split into z-slabs
 (strong scaling, fixed 512^3) with RCCL halo exchanges.  Rank 0 prints one
 JSON line.
 
-V-cycles/s are measured on a second solver built like a real solve
+V-cycles/s (--full) are measured on a second solver built like a real solve
 (CycleType VCYCLE: dense rhs layout, the production V-cycle), not on the
 SMOOTHER-mode solver of the sweep measurement.
 """
@@ -38,6 +42,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed steps: the sustained window, V-cycles/s, the mad_run cycle cost "
+                        "per precision, the solve to 1e-10 and the CPU baseline (each a run of its own)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the level-0 iterate the last step left as "
+                        "DIR/x.npy (float32; above 8 Mi voxels a fixed seeded sample of it)")
     # untimed sweeps after setup, before the W warm-up steps: the clocks and power take ~20-30 launches
     # (~30 ms) to reach their steady state after the device idled (profiles/r06_clock_summaries.log)
     p.add_argument("--settle-ms", type=float, default=150.0)
@@ -279,6 +289,24 @@ def load_traffic(tag, kernel_sig):
     return None
 
 
+DUMP_MAX_VOXELS = 8 << 20   # 32 MB of float32 over all ranks' files
+
+
+def dump_outputs(outdir, x, rank, world):
+    """--dump-outputs: the iterate `x` (this rank's slab of level 0 after the last timed sweep) as
+    float32 -- the solver's own precision -- in DIR/x.npy (DIR/x.rank<r>.npy on N > 1 ranks).
+    Whole when the slab has at most DUMP_MAX_VOXELS / N voxels, else its values at that many flat
+    indices drawn from a fixed seed: the same voxels in every run of the same shape."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    out = np.ascontiguousarray(x, dtype=np.float32)
+    cap = DUMP_MAX_VOXELS // world
+    if out.size > cap:
+        idx = np.random.default_rng(20).integers(0, out.size, size=cap)
+        out = out.reshape(-1)[idx]
+    np.save(os.path.join(outdir, "x.npy" if world == 1 else f"x.rank{rank}.npy"), out)
+
+
 T0 = time.perf_counter()
 
 
@@ -422,50 +450,55 @@ def main():
     per_launch = sorted(launch_series)
     if world > 1:
         wall = float(s.allreduce([wall], "max")[0])
-    # beside the contract's K steps (24 ms at K = 20): a sustained window of ~2 s of the same
-    # sweeps, device-timed, so the rate is also measured over a span a utilisation sampler sees
-    sus_n = max(a.steps, int(2000.0 / max(wall / a.steps * 1e3, 0.05)))
-    phase(rank, f"sweeps: sustained window of {sus_n}")
-    sus_dev, sus_kern, _ = s.bench_smooth(0, sus_n)
-    sus_series = list(s.bench_launch_times())
-    sus_win = [round(sum(sus_series[q:q + 100]) / len(sus_series[q:q + 100]), 4)
-               for q in range(0, len(sus_series), 100)]
-    if world > 1:
-        sus_dev = float(s.allreduce([sus_dev], "max")[0])
+    if a.dump_outputs:
+        phase(rank, f"writing the iterate after the last timed step to {a.dump_outputs}")
+        dump_outputs(a.dump_outputs, s.download(0, M.capi.X), rank, world)
+    if a.full:
+        # beside the contract's K steps (24 ms at K = 20): a sustained window of ~2 s of the same
+        # sweeps, device-timed, so the rate is also measured over a span a utilisation sampler sees
+        sus_n = max(a.steps, int(2000.0 / max(wall / a.steps * 1e3, 0.05)))
+        phase(rank, f"sweeps: sustained window of {sus_n}")
+        sus_dev, sus_kern, _ = s.bench_smooth(0, sus_n)
+        sus_series = list(s.bench_launch_times())
+        sus_win = [round(sum(sus_series[q:q + 100]) / len(sus_series[q:q + 100]), 4)
+                   for q in range(0, len(sus_series), 100)]
+        if world > 1:
+            sus_dev = float(s.allreduce([sus_dev], "max")[0])
     nvox = float(S) ** 3
     value = nvox * a.steps / wall / 1e6
     info = s.level_info(0)
     nlev = s.num_levels
     kname = s.smooth_kernel_name(0)  # as rocprofv3 prints it (profiles/ are matched on it)
     s.close()
-    # V-cycles/s (same volume, nu = 2) on a solver in the production layout (CycleType
-    # VCYCLE: level-0 records without b, dense rhs), as GenerateData runs it; the halo form
-    # the sweep measurement settled on
-    s = make(M.VCYCLE, opts, "vcycle")
-    vplacement = s.placement_trials()
-    vnote = None
-    if opts and a.halo == "auto":
-        # the V-cycle's distributed levels push too (per-colour levels after their last colour
-        # pass): checked against the RCCL exchange like the sweeps
-        ok, why = verify_peer(M, s, make, rank, steps=3, vcycles=True)
-        vnote = why if ok else f"V-cycle peer halo rejected ({why}): rccl"
-        if not ok:
-            s.close()
-            s = make(M.VCYCLE, 0, "vcycle-rccl")
-    s.vcycle()
-    # untimed cycles as the sweeps' settle phase (same count on every rank: ~settle_ms at ~6 sweeps each)
-    settle_vc = int(math.ceil(settle / 6.0)) if settle else 0
-    if settle_vc:
-        s.bench_vcycle(settle_vc)
-    barrier()
-    t1 = time.perf_counter()
-    phase(rank, f"V-cycles: {settle_vc} settle + {a.vcycles} timed")
-    vc_ms = s.bench_vcycle(a.vcycles)
-    barrier()
-    vwall = time.perf_counter() - t1
-    if world > 1:
-        vwall = float(s.allreduce([vwall], "max")[0])
-    s.close()
+    if a.full:
+        # V-cycles/s (same volume, nu = 2) on a solver in the production layout (CycleType
+        # VCYCLE: level-0 records without b, dense rhs), as GenerateData runs it; the halo form
+        # the sweep measurement settled on
+        s = make(M.VCYCLE, opts, "vcycle")
+        vplacement = s.placement_trials()
+        vnote = None
+        if opts and a.halo == "auto":
+            # the V-cycle's distributed levels push too (per-colour levels after their last colour
+            # pass): checked against the RCCL exchange like the sweeps
+            ok, why = verify_peer(M, s, make, rank, steps=3, vcycles=True)
+            vnote = why if ok else f"V-cycle peer halo rejected ({why}): rccl"
+            if not ok:
+                s.close()
+                s = make(M.VCYCLE, 0, "vcycle-rccl")
+        s.vcycle()
+        # untimed cycles as the sweeps' settle phase (same count on every rank: ~settle_ms at ~6 sweeps each)
+        settle_vc = int(math.ceil(settle / 6.0)) if settle else 0
+        if settle_vc:
+            s.bench_vcycle(settle_vc)
+        barrier()
+        t1 = time.perf_counter()
+        phase(rank, f"V-cycles: {settle_vc} settle + {a.vcycles} timed")
+        vc_ms = s.bench_vcycle(a.vcycles)
+        barrier()
+        vwall = time.perf_counter() - t1
+        if world > 1:
+            vwall = float(s.allreduce([vwall], "max")[0])
+        s.close()
 
     if rank != 0:
         return
@@ -515,22 +548,27 @@ def main():
                              if "peer halo" in kname else "rccl: grouped send/recv after each sweep")
                             + (f"; {halo_note}" if halo_note else "")),
                    "slab_shape": list(info["shape"])},
+        "device_ms_per_step": round(dev_ms / a.steps, 4),
+        "roofline": roof,
+        # the level-0 sweep ms (forward, reverse direction) of every set of arrays setup tried, the
+        # fastest kept (mad_placement_trials, DESIGN.md "Placement"): which speeds this box offered
+        "placement_trials_ms": [round(v, 4) for v in placement],
+    }
+    if not a.full:
+        print(json.dumps(line), flush=True)
+        return
+    line.update({
         "vcycles_per_s": round(a.vcycles / vwall, 3),
         "vcycle_config": "CycleType VCYCLE (dense rhs layout), nu = 2, 4-colour GS, "
                          f"{nlev} levels, graph-replayed per rank" + (f"; {vnote}" if vnote else ""),
         "device_ms_per_vcycle": round(vc_ms / a.vcycles, 3),
         "ms_per_vcycle": round(vwall / a.vcycles * 1e3, 3),
-        "device_ms_per_step": round(dev_ms / a.steps, 4),
         "sustained": {"steps": sus_n, "device_ms_per_step": round(sus_dev / sus_n, 4),
                       "kernel_ms_mean": round(sus_kern, 5),
                       "kernel_ms_per_100": sus_win,
                       "value": round(nvox * sus_n / (sus_dev * 1e-3) / 1e6, 1)},
-        "roofline": roof,
-        # the level-0 sweep ms (forward, reverse direction) of every set of arrays setup tried, the
-        # fastest kept (mad_placement_trials, DESIGN.md "Placement"): which speeds this box offered
-        "placement_trials_ms": [round(v, 4) for v in placement],
         "vcycle_placement_trials_ms": [round(v, 4) for v in vplacement],  # the V-cycle layout's level-0 sweep
-    }
+    })
     if world == 1 and not a.no_precision_cycles:
         # the cycle mad_run runs at the reference tests' Tolerance 1e-10 (MAD_PRECISION_AUTO ->
         # FP32_REFINE: fp32 V-cycle + fp64 residual / update), and in MAD_FP64 (the reference's

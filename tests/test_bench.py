@@ -46,7 +46,7 @@ def test_cpu_baseline_falls_back_when_over_its_time_bound():
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--smoother", "wj"], ["--gs-kernel", "1"]])
 def test_bench_json_line(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "256", "--steps", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--size", "256", "--steps", "4",
            "--warmup", "1", "--vcycles", "2", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -74,6 +74,76 @@ def test_bench_json_line(extra):
     assert r["launches"] == 4 * nl
     assert r["algorithmic_bytes_per_launch"] == 36.0 * 256 ** 3 / nl
     assert 0 < r["kernel_ms_min"] <= r["kernel_ms_median"]
+
+
+FULL_ONLY = ("vcycles_per_s", "ms_per_vcycle", "sustained", "run_ms_per_cycle", "solve_1e-10",
+             "refine_vcycles_per_s", "fp64_vcycles_per_s", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the run is setup, settle, warm-up and the timed steps only: the line holds
+    the headline keys and none of the figures that take runs of their own, --steps is the number
+    of timed sweeps, and --dump-outputs writes the iterate the last of them left -- equal, bit
+    for bit, to the same count of sweeps of the same synthetic system run here."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import multigridanisotropicdiffusion_amd as M
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "256", "--steps", "5",
+           "--warmup", "2", "--dump-outputs", str(tmp_path / "got")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+              "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["unit"] == "Mvoxel-smooths/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["roofline"]["launches"] == 5
+    assert abs(d["value"] - 256 ** 3 * 5 / (d["ms_per_step"] * 5e-3) / 1e6) <= 0.01 * d["value"]
+    assert "sustained" not in out.stderr and "V-cycles" not in out.stderr  # the phases did not run
+
+    got = np.load(tmp_path / "got" / "x.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_MAX_VOXELS,) and got.nbytes <= 64 << 20
+    shape = (256, 256, 256)
+    s = M.Solver(shape, (1.0, 1.0, 1.0), time_step=0.1, smoother=M.GAUSS_SEIDEL, precision=M.FP32,
+                 cycle=M.SMOOTHER, global_shape=shape)
+    s.synth_tensor(kind=0, seed=4)
+    s.setup()
+    s.synth_level(0, M.capi.B, 3)
+    s.synth_level(0, M.capi.X, 3)
+    s.smooth(0, d["settle_sweeps"] + 2 + 5)
+    ref = s.download(0, M.capi.X)
+    s.close()
+    bench.dump_outputs(str(tmp_path / "ref"), ref, 0, 1)
+    want = np.load(tmp_path / "ref" / "x.npy")
+    assert np.isfinite(got).all() and got.std() > 0
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """dump_outputs: float32, the whole array up to DUMP_MAX_VOXELS (over all ranks), beyond it
+    the values at the same seeded flat indices in every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_MAX_VOXELS * 4 <= 64 << 20
+    x = np.random.default_rng(1).random((6, 7, 8))
+    bench.dump_outputs(str(tmp_path / "a"), x, 0, 1)
+    a = np.load(tmp_path / "a" / "x.npy")
+    assert a.dtype == np.float32 and a.shape == x.shape and np.array_equal(a, x.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_VOXELS", 100)
+    bench.dump_outputs(str(tmp_path / "b"), x, 0, 1)
+    bench.dump_outputs(str(tmp_path / "c"), x + 1.0, 0, 1)
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert b.dtype == np.float32 and b.shape == (100,) and set(b) <= set(a.reshape(-1))
+    assert np.allclose(c - b, 1.0, atol=1e-6)  # the same voxels both times
+    # N ranks share the bound: each writes its slab's file with a 1/N share
+    bench.dump_outputs(str(tmp_path / "b"), x, 1, 2)
+    assert np.load(tmp_path / "b" / "x.rank1.npy").shape == (50,)
 
 
 def test_gpus_must_match_world_size():
@@ -170,7 +240,7 @@ def test_bench_two_ranks_on_one_gpu(halo):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--size", "256", "--steps", "4", "--warmup", "1", "--vcycles", "2",
+           "--gpus", "2", "--full", "--size", "256", "--steps", "4", "--warmup", "1", "--vcycles", "2",
            "--no-cpu-baseline", "--no-precision-cycles", "--halo", halo]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=150, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

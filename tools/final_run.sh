@@ -8,7 +8,7 @@ bash tools/gpu_steps.sh \
   "${T}_build|600|python -c 'import __graft_entry__ as g; g.build()'" \
   "${T}_gputests|1100|python -u -m pytest tests -m gpu -x -q --timeout 900 --timeout-method thread" \
   "${T}_smoke|300|python -c 'import __graft_entry__ as g; g.smoke()'" \
-  "${T}_bench|300|python bench.py" \
+  "${T}_bench|300|python bench.py --full" \
   "${T}_prof|900|bash tools/profile_round.sh ${T}_prof" \
   "${T}_vcycle_prof|700|bash tools/vcycle_profiles.sh"
 # (not part of the driver's run) the bench's N = 2 torchrun launch and V-cycle forms with two RCCL

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench \
-    -- python3 bench.py --no-cpu-baseline $BARGS > "$OUT/trace.log" 2>&1
+    -- python3 bench.py --full --no-cpu-baseline $BARGS > "$OUT/trace.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -o fetch \
     -- python3 tools/profile_traffic.py $TARGS > "$OUT/fetch.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -o write \
