@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -54,6 +55,42 @@ struct MadError : std::runtime_error {
   do {                           \
     if (!(cond)) throw MadError((code), (msg)); \
   } while (0)
+
+// a timing event owned by its scope: a throw between create and destroy leaks nothing
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() { HIP_CHECK(hipEventCreate(&e)); }
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  operator hipEvent_t() const { return e; }
+};
+
+float elapsed(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+  return ms;
+}
+
+// a flag set for a scope and false again on every exit from it, a throw included
+struct FlagScope {
+  bool& flag;
+  explicit FlagScope(bool& f, bool v = true) : flag(f) { flag = v; }
+  FlagScope(const FlagScope&) = delete;
+  ~FlagScope() { flag = false; }
+};
+
+// fp32 floor guard: the best relres of the last `window` cycles is within 1% of the best before them
+// (only while the tolerance is unmet: a cycle that reaches it ends the step as converged)
+bool stalled_at(const std::vector<double>& hist, size_t window, double tolerance) {
+  if (!(hist.size() > window && hist.back() < 1e-3 && hist.back() > tolerance)) return false;
+  const double prev_best = *std::min_element(hist.begin(), hist.end() - window);
+  const double recent = *std::min_element(hist.end() - window, hist.end());
+  return recent > 0.99 * prev_best;
+}
 
 thread_local std::string g_last_error;
 
@@ -547,8 +584,7 @@ class Solver final : public SolverBase {
         bench_smooth(l, n, &tot_ms, &kern, &q);
         return;
       }
-      std::vector<hipEvent_t> ev(2 * n);
-      for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+      std::vector<Event> ev(2 * n);
       for (unsigned i = 0; i < n; ++i) {
         HIP_CHECK(hipEventRecord(ev[2 * i], c_->stream));
         launch_fused_part(L, 0);
@@ -558,8 +594,7 @@ class Solver final : public SolverBase {
       }
       HIP_CHECK(hipEventSynchronize(ev[2 * n - 1]));
       launch_ms.assign(n, 0.f);
-      for (unsigned i = 0; i < n; ++i) HIP_CHECK(hipEventElapsedTime(&launch_ms[i], ev[2 * i], ev[2 * i + 1]));
-      for (auto& e : ev) (void)hipEventDestroy(e);
+      for (unsigned i = 0; i < n; ++i) launch_ms[i] = elapsed(ev[2 * i], ev[2 * i + 1]);
     };
     // mean ms of the two launches in each direction: 0 and 2 read x and write t, 1 and 3 the reverse
     auto time_dirs = [&](double* fwd, double* rev) {
@@ -1071,12 +1106,17 @@ class Solver final : public SolverBase {
     const PeerOut<T> po = part == 4 ? peer_out(L, buffer_index(L, L.t)) : PeerOut<T>{{nullptr, nullptr}, {nullptr, nullptr}};
     auto run = [&](auto kern) {
       // every instance that can be launched gets its dynamic-LDS opt-in (a kernel pointer
-      // set, not one flag per function type: several instances share one signature)
-      static std::vector<const void*> attr;
-      if (std::find(attr.begin(), attr.end(), (const void*)kern) == attr.end()) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-        attr.push_back((const void*)kern);
+      // set, not one flag per function type: several instances share one signature); the set is
+      // shared by the rank threads of the in-process transport, whose first launches coincide
+      {
+        static std::mutex attr_mu;
+        static std::vector<const void*> attr;
+        std::lock_guard<std::mutex> lk(attr_mu);
+        if (std::find(attr.begin(), attr.end(), (const void*)kern) == attr.end()) {
+          HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds));
+          attr.push_back((const void*)kern);
+        }
       }
       hipLaunchKernelGGL(kern, dim3(nb), dim3(NT), lds, c_->stream, L.x, L.t, L.bs ? L.bs : L.b, L.cf, L.g,
                          L.rat, zr.zc, ntx, nty, zr.zbase, zr.zstride, flip, sig, po);
@@ -1298,7 +1338,7 @@ class Solver final : public SolverBase {
                                std::is_same<T, double>::value, c_->comm_stream);
       HIP_CHECK(hipEventRecord(L.ev_halo, c_->comm_stream));
     } else if (!overlap) {
-      // the first sweep of a refine correction cycle (x zero by construction, run_refine), or of a
+      // the first sweep of a refine correction cycle (x zero by construction, run's refine_), or of a
       // coarse level whose descent left its zero x unwritten (x_zero_lazy)
       const bool zu = (zero_x0_ && &L == &lv_[0]) || L.x_zero_lazy;
       zero_x0_ = false;
@@ -1452,7 +1492,7 @@ class Solver final : public SolverBase {
   // fp64 residual of the refined level-0 system: r64 = b64 - A64 u64 (+ ||r||^2 partials),
   // the reference operator in fp64 (coefficient records cf64_, g from the fp64 tensor).  3D
   // levels of >= 16 x 16 write the fp32 hierarchy's next rhs b = (T) r and x = 0 in the same
-  // pass instead of r64 (refine_emitted_; else run_refine converts r64 and fills x)
+  // pass instead of r64 (refine_emitted_; else run converts r64 and fills x)
   bool refine_emitted_ = false;
   bool refine_emitted_bs_ = false;  // ... and the split copy of b (LevelData::bs) with it
   // fold: u += (double) x (the fp32 cycle's correction) in the same pass -- one GPU, resid3_k levels:
@@ -2082,15 +2122,21 @@ class Solver final : public SolverBase {
   }
 
   // ------------------------------------------------------------- filter
+  // GenerateData (MAD.hxx:104-297): the rhs b and the iterate x of level 0 in T.
+  // With mixed-precision defect correction (refine_, MAD_FP32_REFINE) the iterate u and the
+  // rhs b of level 0 stay in fp64; every cycle forms the fp64 residual
+  // r = b - A u with the fp64 operator, runs the cycle the CycleType names (one V-cycle, or
+  // one smoother sweep) in fp32 on the error equation A e = r from e = 0, and adds u += e in
+  // fp64.  The fp32 V-cycle only has to reduce the error by its usual factor each time, so
+  // the iteration converges to the fp64 solution (relres to the reference's 1e-10) instead
+  // of stalling at the fp32 floor (~1e-7); relres is the fp64 residual's, as in the
+  // reference's loop (MAD.hxx:207-246).  FMG: the fp32 FMG cycle gives the first iterate.
   void run(const void* in, int in_dtype, void* out, int out_dtype, bool dev_io,
            mad_stats* st) override {
-    if (refine_) {
-      run_refine(in, in_dtype, out, out_dtype, dev_io, st);
-      return;
-    }
     LevelData<T>& L0 = lv_[0];
     const int64_t N = L0.g.N;
     const mad_desc& d = c_->d;
+    const unsigned nb = flat_blocks(N);
     // cast input -> internal precision (MAD.hxx:110-127)
     const void* src = in;
     if (!dev_io) {
@@ -2099,159 +2145,31 @@ class Solver final : public SolverBase {
                                c_->stream));
       src = stage;
     }
-    convert_in(src, in_dtype, L0.b, N);
-    L0.b_halo_ok = L0.brec_ok = false;
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    HIP_CHECK(hipEventRecord(e0, c_->stream));
-    c_->step_cycles.clear();
-    c_->step_relres.clear();
-    c_->trace.clear();
-    // per-cycle entries (seconds since the run's start); with MAD_OPT_BENCHMARK_TRACE the V-cycle
-    // records level 0's entries itself (per_sweep_line) and only SMOOTHER sweeps are recorded here,
-    // with seconds since the time step's start (the reference's m_Time, MAD.hxx:158-163)
-    const bool bt = c_->bench_trace();
-    c_->trace_active = true;
-    c_->trace_t0 = std::chrono::steady_clock::now();
-    auto trace = [&](unsigned step, double rr) {
-      if (bt && d.cycle != MAD_SMOOTHER) return;
-      c_->trace_step = step;
-      c_->trace_push(rr);
-    };
-    bool stalled_any = false;
-    unsigned total = 0;
-    double relres = 0.0;
-    for (unsigned step = 0; step < d.number_of_steps; ++step) {  // MAD.hxx:158
-      if (d.verbose && d.number_of_steps > 1 && c_->comm.rank() == 0)
-        std::printf("\n------------ Time step n. %u / %u------------\n", step + 1, d.number_of_steps);
-      if (bt) {
-        c_->trace_t0 = std::chrono::steady_clock::now();
-        c_->trace_step = step;
-        c_->trace_rhs = norm(0, MAD_B);  // the rhsNorm of the step's level-0 V-cycles (MAD.hxx:352)
+    if (refine_) {
+      convert_to(src, in_dtype, b64_, N, c_->stream);
+      // an 8/16-bit or fp32 image is exactly an fp32 array: the first time step's fp64 residuals read
+      // its fp32 copy (the same values, 4 of the pass's 104 B per voxel saved)
+      b32_exact_ = in_dtype == MAD_U8 || in_dtype == MAD_I8 || in_dtype == MAD_U16 || in_dtype == MAD_I16 ||
+                   in_dtype == MAD_F32;
+      if (b32_exact_) {
+        hipLaunchKernelGGL((convert_k<double, float>), dim3(nb), dim3(256), 0, c_->stream, b64_, b32_, N);
+        HIP_CHECK(hipGetLastError());
       }
-      if (d.cycle == MAD_FMG) {
-        if (d.verbose && c_->comm.rank() == 0) std::printf("|--- Full Multigrid Cycle ---|\n");
-        fmg_rec(0);  // MAD.hxx:170-176
-      } else {
-        HIP_CHECK(hipMemcpyAsync(L0.x, L0.b, sizeof(T) * N, hipMemcpyDeviceToDevice,
-                                 c_->stream));  // MAD.hxx:177-201
-        x_changed(0);
-      }
-      const double rhsNorm = norm(0, MAD_B);  // MAD.hxx:204
-      REQUIRE(std::isfinite(rhsNorm), MAD_ERR_NUMERIC,
-              "non-finite right-hand side norm (NaN/Inf in the input image)");
-      unsigned it = 0;
-      double best = INFINITY;
-      std::vector<double> hist;
-      const unsigned window = (d.cycle == MAD_SMOOTHER) ? 50 : 5;
-      bool stalled = false;
-      do {  // MAD.hxx:207-246
-        if (d.cycle == MAD_SMOOTHER) {
-          smooth(0, 1);
-        } else {
-          if (d.verbose && c_->comm.rank() == 0) std::printf("\n|--- VCycle n. %u ---|\n", it + 1);
-          vcycle_fast();
-        }
-        const double resNorm = residual_impl(0, true, false);  // MAD.hxx:221-229 (norm only)
-        // NaN > tol is false: without this check a NaN residual ends the do/while as if
-        // converged and the call returns MAD_OK with a NaN image
-        REQUIRE(std::isfinite(resNorm), MAD_ERR_NUMERIC,
-                "non-finite residual norm (NaN/Inf in the tensor or the iterate)");
-        // an all-zero image (rhsNorm 0) is its own solution: report relres 0, not 0/0
-        relres = (rhsNorm > 0.0) ? resNorm / rhsNorm : resNorm;
-        if (d.verbose && d.cycle == MAD_SMOOTHER && c_->comm.rank() == 0)
-          std::printf("Smoother iteration n. %u: relative residual = %g\n", it + 1, relres);
-        ++it;
-        trace(step, relres);
-        hist.push_back(relres);
-        // fp32 floor guard: best relres not improved by 1% within `window` cycles (only while the
-        // tolerance is unmet: a cycle that reaches it ends the step as converged)
-        if (d.stall_guard && hist.size() > window && relres < 1e-3 && relres > d.tolerance) {
-          double prev_best = INFINITY;
-          for (size_t q = 0; q + window < hist.size(); ++q) prev_best = std::min(prev_best, hist[q]);
-          double recent = INFINITY;
-          for (size_t q = hist.size() - window; q < hist.size(); ++q) recent = std::min(recent, hist[q]);
-          if (recent > 0.99 * prev_best) stalled = true;
-        }
-        best = std::min(best, relres);
-      } while (relres > d.tolerance && it < d.max_cycles && !stalled);
-      stalled_any |= stalled;
-      total += it;
-      c_->step_cycles.push_back(it);
-      c_->step_relres.push_back(relres);
-      HIP_CHECK(hipMemcpyAsync(L0.b, L0.x, sizeof(T) * N, hipMemcpyDeviceToDevice,
-                               c_->stream));  // MAD.hxx:248-261
+    } else {
+      convert_in(src, in_dtype, L0.b, N);
       L0.b_halo_ok = L0.brec_ok = false;
-    }
-    c_->trace_active = false;
-    HIP_CHECK(hipEventRecord(e1, c_->stream));
-    // cast solution -> output type (MAD.hxx:266-289)
-    void* dst = out;
-    if (!dev_io) dst = scratch_bytes(N * dtype_size(out_dtype));
-    convert_out(L0.x, dst, out_dtype, N);
-    if (!dev_io)
-      HIP_CHECK(hipMemcpyAsync(out, dst, N * dtype_size(out_dtype), hipMemcpyDeviceToHost,
-                               c_->stream));
-    HIP_CHECK(hipStreamSynchronize(c_->stream));
-    peer_check();  // a timed-out peer wait fails the run instead of returning stale halos
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    HIP_CHECK(hipEventDestroy(e0));
-    HIP_CHECK(hipEventDestroy(e1));
-    if (st) {
-      std::memset(st, 0, sizeof(*st));
-      st->steps = d.number_of_steps;
-      st->total_cycles = total;
-      st->last_cycles = c_->step_cycles.empty() ? 0 : c_->step_cycles.back();
-      st->stalled = stalled_any ? 1 : 0;
-      st->last_relres = relres;
-      st->setup_ms = c_->setup_ms;
-      st->solve_ms = ms;
-      st->num_levels = (uint32_t)c_->nlev;
-      st->tensor_kind = c_->kind;
-      st->colors = c_->ncolors;
-    }
-  }
-
-  // GenerateData (MAD.hxx:104-297) with mixed-precision defect correction (MAD_FP32_REFINE):
-  // the iterate u and the rhs b of level 0 stay in fp64; every cycle forms the fp64 residual
-  // r = b - A u with the fp64 operator, runs the cycle the CycleType names (one V-cycle, or
-  // one smoother sweep) in fp32 on the error equation A e = r from e = 0, and adds u += e in
-  // fp64.  The fp32 V-cycle only has to reduce the error by its usual factor each time, so
-  // the iteration converges to the fp64 solution (relres to the reference's 1e-10) instead
-  // of stalling at the fp32 floor (~1e-7); relres is the fp64 residual's, as in the
-  // reference's loop (MAD.hxx:207-246).  FMG: the fp32 FMG cycle gives the first iterate.
-  void run_refine(const void* in, int in_dtype, void* out, int out_dtype, bool dev_io,
-                  mad_stats* st) {
-    LevelData<T>& L0 = lv_[0];
-    const int64_t N = L0.g.N;
-    const mad_desc& d = c_->d;
-    const unsigned nb = flat_blocks(N);
-    const void* src = in;
-    if (!dev_io) {
-      void* stage = scratch_bytes(N * dtype_size(in_dtype));
-      HIP_CHECK(hipMemcpyAsync(stage, in, N * dtype_size(in_dtype), hipMemcpyHostToDevice,
-                               c_->stream));
-      src = stage;
-    }
-    convert_to(src, in_dtype, b64_, N, c_->stream);
-    // an 8/16-bit or fp32 image is exactly an fp32 array: the first time step's fp64 residuals read
-    // its fp32 copy (the same values, 4 of the pass's 104 B per voxel saved)
-    b32_exact_ = in_dtype == MAD_U8 || in_dtype == MAD_I8 || in_dtype == MAD_U16 || in_dtype == MAD_I16 ||
-                 in_dtype == MAD_F32;
-    if (b32_exact_) {
-      hipLaunchKernelGGL((convert_k<double, float>), dim3(nb), dim3(256), 0, c_->stream, b64_, b32_, N);
-      HIP_CHECK(hipGetLastError());
     }
     auto to_fp32_rhs = [&](const double* a) {  // level-0 b (fp32) <- a
       hipLaunchKernelGGL((convert_k<double, T>), dim3(nb), dim3(256), 0, c_->stream, a, L0.b, N);
       HIP_CHECK(hipGetLastError());
       L0.b_halo_ok = L0.brec_ok = false;
     };
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
+    auto x_to_u64 = [&] {
+      hipLaunchKernelGGL((convert_k<T, double>), dim3(nb), dim3(256), 0, c_->stream, L0.x, u64_, N);
+      HIP_CHECK(hipGetLastError());
+    };
+    auto rhs_norm = [&] { return refine_ ? norm64(b64_) : norm(0, MAD_B); };  // MAD.hxx:204 / 352
+    Event e0, e1;
     HIP_CHECK(hipEventRecord(e0, c_->stream));
     c_->step_cycles.clear();
     c_->step_relres.clear();
@@ -2260,20 +2178,15 @@ class Solver final : public SolverBase {
     // records level 0's entries itself (per_sweep_line) and only SMOOTHER sweeps are recorded here,
     // with seconds since the time step's start (the reference's m_Time, MAD.hxx:158-163)
     const bool bt = c_->bench_trace();
-    c_->trace_active = true;
+    FlagScope tracing(c_->trace_active);
     c_->trace_t0 = std::chrono::steady_clock::now();
-    auto trace = [&](unsigned step, double rr) {
-      if (bt && d.cycle != MAD_SMOOTHER) return;
-      c_->trace_step = step;
-      c_->trace_push(rr);
-    };
     bool stalled_any = false;
     unsigned total = 0;
     double relres = 0.0;
     for (unsigned step = 0; step < d.number_of_steps; ++step) {  // MAD.hxx:158
       if (d.verbose && d.number_of_steps > 1 && c_->comm.rank() == 0)
         std::printf("\n------------ Time step n. %u / %u------------\n", step + 1, d.number_of_steps);
-      // V-cycle / FMG solves start in plain fp32 (the fp32 iterate on the fp32 rhs, fp32 residual
+      // refined V-cycle / FMG solves start in plain fp32 (the fp32 iterate on the fp32 rhs, fp32 residual
       // norms) while relres is far above fp32's floor: those cycles reduce the error as the refined
       // ones would, at the fp32 cycle's cost; below MAD_REFINE_SWITCH_RELRES the iterate moves to
       // fp64 and the defect correction takes over (SMOOTHER runs refine from the first sweep: their
@@ -2282,131 +2195,131 @@ class Solver final : public SolverBase {
       const bool fp32_phase = false;
 #else
       // (at least two cycles allowed: the fp32 phase always leaves the defect correction a turn)
-      const bool fp32_phase = d.cycle != MAD_SMOOTHER && d.max_cycles >= 2;
+      const bool fp32_phase = refine_ && d.cycle != MAD_SMOOTHER && d.max_cycles >= 2;
 #endif
       if (bt) {
         c_->trace_t0 = std::chrono::steady_clock::now();
         c_->trace_step = step;
-        c_->trace_rhs = norm64(b64_);  // MAD.hxx:204 / 352
+        c_->trace_rhs = rhs_norm();  // the rhsNorm of the step's level-0 V-cycles
       }
+      // the first iterate: the FMG cycle's, or the rhs (MAD.hxx:170-201); in fp32 unless refined
+      // without the fp32 phase
+      if (refine_ && (d.cycle == MAD_FMG || fp32_phase)) to_fp32_rhs(b64_);
       if (d.cycle == MAD_FMG) {
         if (d.verbose && c_->comm.rank() == 0) std::printf("|--- Full Multigrid Cycle ---|\n");
-        to_fp32_rhs(b64_);
-        fmg_rec(0);  // MAD.hxx:170-176, in fp32
-        if (!fp32_phase) {
-          hipLaunchKernelGGL((convert_k<T, double>), dim3(nb), dim3(256), 0, c_->stream, L0.x, u64_, N);
-          HIP_CHECK(hipGetLastError());
-        }
-      } else if (fp32_phase) {
-        to_fp32_rhs(b64_);
-        HIP_CHECK(hipMemcpyAsync(L0.x, L0.b, sizeof(T) * N, hipMemcpyDeviceToDevice,
-                                 c_->stream));  // MAD.hxx:177-201
+        fmg_rec(0);
+        if (refine_ && !fp32_phase) x_to_u64();
+      } else if (!refine_ || fp32_phase) {
+        HIP_CHECK(hipMemcpyAsync(L0.x, L0.b, sizeof(T) * N, hipMemcpyDeviceToDevice, c_->stream));
         x_changed(0);
       } else {
-        HIP_CHECK(hipMemcpyAsync(u64_, b64_, sizeof(double) * N, hipMemcpyDeviceToDevice,
-                                 c_->stream));  // MAD.hxx:177-201
+        HIP_CHECK(hipMemcpyAsync(u64_, b64_, sizeof(double) * N, hipMemcpyDeviceToDevice, c_->stream));
       }
-      const double rhsNorm = norm64(b64_);  // MAD.hxx:204
+      const double rhsNorm = rhs_norm();
       REQUIRE(std::isfinite(rhsNorm), MAD_ERR_NUMERIC,
               "non-finite right-hand side norm (NaN/Inf in the input image)");
       unsigned it = 0;
       std::vector<double> hist;
       const unsigned window = (d.cycle == MAD_SMOOTHER) ? 50 : 5;
       bool stalled = false;
+      auto rel = [&](double resNorm) {
+        // NaN > tol is false: without this check a NaN residual ends the do/while as if
+        // converged and the call returns MAD_OK with a NaN image
+        REQUIRE(std::isfinite(resNorm), MAD_ERR_NUMERIC,
+                "non-finite residual norm (NaN/Inf in the tensor or the iterate)");
+        // an all-zero image (rhsNorm 0) is its own solution: report relres 0, not 0/0
+        return (rhsNorm > 0.0) ? resNorm / rhsNorm : resNorm;
+      };
+      auto cycle = [&](bool zero_x0) {  // one sweep or V-cycle on level 0's x and b
+        if (d.cycle == MAD_SMOOTHER) {
+          smooth(0, 1);
+          return;
+        }
+        if (d.verbose && c_->comm.rank() == 0) std::printf("\n|--- VCycle n. %u ---|\n", it + 1);
+        FlagScope zu(zero_x0_, zero_x0);  // x = 0 (or left stale by the fold)
+        vcycle_fast();
+      };
+      auto record = [&](double resNorm) {  // one iteration done (MAD.hxx:221-229)
+        relres = rel(resNorm);
+        if (d.verbose && d.cycle == MAD_SMOOTHER && c_->comm.rank() == 0)
+          std::printf("Smoother iteration n. %u: relative residual = %g\n", it + 1, relres);
+        ++it;
+        hist.push_back(relres);
+        if (!bt || d.cycle == MAD_SMOOTHER) {
+          c_->trace_step = step;
+          c_->trace_push(relres);
+        }
+      };
       if (fp32_phase) {
         do {  // MAD.hxx:207-246 in fp32
-          if (d.verbose && c_->comm.rank() == 0) std::printf("\n|--- VCycle n. %u ---|\n", it + 1);
-          vcycle_fast();
-          const double rn = residual_impl(0, true, false);
-          REQUIRE(std::isfinite(rn), MAD_ERR_NUMERIC,
-                  "non-finite residual norm (NaN/Inf in the tensor or the iterate)");
-          relres = (rhsNorm > 0.0) ? rn / rhsNorm : rn;
-          ++it;
-          trace(step, relres);
-          hist.push_back(relres);
+          cycle(false);
+          record(residual_impl(0, true, false));
           // plain fp32 levels off at a floor that grows with the conditioning (large time steps,
           // strong anisotropy): once a cycle reduces relres by less than 2x, the fp64 defect
           // correction takes over, and the phase ends one cycle before MaxCycles so it always does
           if (hist.size() >= 2 && relres > MAD_REFINE_FP32_MIN_RATE * hist[hist.size() - 2]) break;
         } while (relres > std::max(d.tolerance, MAD_REFINE_SWITCH_RELRES) && it + 1 < d.max_cycles);
-        hipLaunchKernelGGL((convert_k<T, double>), dim3(nb), dim3(256), 0, c_->stream, L0.x, u64_, N);
-        HIP_CHECK(hipGetLastError());
+        x_to_u64();
       }
-      double resNorm = residual64();
-      REQUIRE(std::isfinite(resNorm), MAD_ERR_NUMERIC,
-              "non-finite residual norm (NaN/Inf in the tensor or the iterate)");
-      if (fp32_phase) {  // the switch iterate's relres, now from the fp64 residual
-        relres = (rhsNorm > 0.0) ? resNorm / rhsNorm : resNorm;
-        if (!hist.empty()) {
+      // benchmark trace: a V-cycle's last post-smoothing entry is the updated iterate's, in fp64
+      auto patch_trace = [&] {
+        if (!c_->trace.empty()) c_->trace.back().relres = relres;
+      };
+      if (refine_) {
+        relres = rel(residual64());
+        if (fp32_phase) {  // the switch iterate's relres, now from the fp64 residual
           hist.back() = relres;
-          // (the per-cycle entry; with the benchmark trace the last post-smoothing sweep's)
-          if (!c_->trace.empty()) c_->trace.back().relres = relres;
+          patch_trace();  // (the per-cycle entry too)
         }
       }
       if (!fp32_phase || (relres > d.tolerance && it < d.max_cycles)) do {  // MAD.hxx:207-246
-        if (refine_emitted_) {  // b = (T) r and x = 0 written by residual64's pass
-          L0.b_halo_ok = false;
-          L0.brec_ok = refine_emitted_bs_;  // the split copy of b too
-          x_changed(0);
+        if (!refine_) {
+          cycle(false);
+          record(residual_impl(0, true, false));  // norm only
         } else {
-          to_fp32_rhs(r64_);
-          fill(0, MAD_X, 0.0);
+          if (refine_emitted_) {  // b = (T) r and x = 0 written by residual64's pass
+            L0.b_halo_ok = false;
+            L0.brec_ok = refine_emitted_bs_;  // the split copy of b too
+            x_changed(0);
+          } else {
+            to_fp32_rhs(r64_);
+            fill(0, MAD_X, 0.0);
+          }
+          cycle(refine_emitted_ && zero_sweep_ok());
+          record(residual64(/*fold=*/true));  // u += e first
+          if (bt && d.cycle != MAD_SMOOTHER) patch_trace();
         }
-        if (d.cycle == MAD_SMOOTHER) {
-          smooth(0, 1);
-        } else {
-          if (d.verbose && c_->comm.rank() == 0) std::printf("\n|--- VCycle n. %u ---|\n", it + 1);
-          zero_x0_ = refine_emitted_ && zero_sweep_ok();  // x = 0 (or left stale by the fold)
-          vcycle_fast();
-          zero_x0_ = false;
-        }
-        resNorm = residual64(/*fold=*/true);  // u += e, then MAD.hxx:221-229
-
-        REQUIRE(std::isfinite(resNorm), MAD_ERR_NUMERIC,
-                "non-finite residual norm (NaN/Inf in the tensor or the iterate)");
-        relres = (rhsNorm > 0.0) ? resNorm / rhsNorm : resNorm;
-        if (d.verbose && d.cycle == MAD_SMOOTHER && c_->comm.rank() == 0)
-          std::printf("Smoother iteration n. %u: relative residual = %g\n", it + 1, relres);
-        ++it;
-        trace(step, relres);
-        // benchmark trace: the last post-smoothing entry is the updated iterate's, now in fp64
-        if (bt && d.cycle != MAD_SMOOTHER && !c_->trace.empty()) c_->trace.back().relres = relres;
-        hist.push_back(relres);
-        // fallback only: the fp64 residual keeps falling where plain fp32 stalls
-        if (d.stall_guard && hist.size() > window && relres < 1e-3 && relres > d.tolerance) {
-          double prev_best = INFINITY;
-          for (size_t q = 0; q + window < hist.size(); ++q) prev_best = std::min(prev_best, hist[q]);
-          double recent = INFINITY;
-          for (size_t q = hist.size() - window; q < hist.size(); ++q) recent = std::min(recent, hist[q]);
-          if (recent > 0.99 * prev_best) stalled = true;
-        }
+        // (refined: fallback only, the fp64 residual keeps falling where plain fp32 stalls)
+        stalled = d.stall_guard && stalled_at(hist, window, d.tolerance);
       } while (relres > d.tolerance && it < d.max_cycles && !stalled);
       stalled_any |= stalled;
       total += it;
       c_->step_cycles.push_back(it);
       c_->step_relres.push_back(relres);
-      HIP_CHECK(hipMemcpyAsync(b64_, u64_, sizeof(double) * N, hipMemcpyDeviceToDevice,
-                               c_->stream));  // MAD.hxx:248-261
-      b32_exact_ = false;  // the next step's rhs is the fp64 solution
+      // the solution is the next step's rhs (MAD.hxx:248-261)
+      if (refine_) {
+        HIP_CHECK(hipMemcpyAsync(b64_, u64_, sizeof(double) * N, hipMemcpyDeviceToDevice, c_->stream));
+        b32_exact_ = false;
+      } else {
+        HIP_CHECK(hipMemcpyAsync(L0.b, L0.x, sizeof(T) * N, hipMemcpyDeviceToDevice, c_->stream));
+        L0.b_halo_ok = L0.brec_ok = false;
+      }
     }
-    c_->trace_active = false;
     HIP_CHECK(hipEventRecord(e1, c_->stream));
     // the last folded residual left x holding the last fp32 correction (the zero-iterate sweep
     // never needed it cleared): leave level-0 x = 0, as the unfolded pass does, for direct
     // kernel-API use after the run (mad_download, mad_smooth, mad_vcycle)
-    if (refine_emitted_ && zero_sweep_ok()) fill(0, MAD_X, 0.0);
+    if (refine_ && refine_emitted_ && zero_sweep_ok()) fill(0, MAD_X, 0.0);
+    // cast solution -> output type (MAD.hxx:266-289)
     void* dst = out;
     if (!dev_io) dst = scratch_bytes(N * dtype_size(out_dtype));
-    convert_from(u64_, dst, out_dtype, N, c_->stream);  // MAD.hxx:266-289
+    if (refine_) convert_from(u64_, dst, out_dtype, N, c_->stream);
+    else convert_out(L0.x, dst, out_dtype, N);
     if (!dev_io)
       HIP_CHECK(hipMemcpyAsync(out, dst, N * dtype_size(out_dtype), hipMemcpyDeviceToHost,
                                c_->stream));
     HIP_CHECK(hipStreamSynchronize(c_->stream));
     peer_check();  // a timed-out peer wait fails the run instead of returning stale halos
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    HIP_CHECK(hipEventDestroy(e0));
-    HIP_CHECK(hipEventDestroy(e1));
     if (st) {
       std::memset(st, 0, sizeof(*st));
       st->steps = d.number_of_steps;
@@ -2415,7 +2328,7 @@ class Solver final : public SolverBase {
       st->stalled = stalled_any ? 1 : 0;
       st->last_relres = relres;
       st->setup_ms = c_->setup_ms;
-      st->solve_ms = ms;
+      st->solve_ms = elapsed(e0, e1);
       st->num_levels = (uint32_t)c_->nlev;
       st->tensor_kind = c_->kind;
       st->colors = c_->ncolors;
@@ -2431,11 +2344,8 @@ class Solver final : public SolverBase {
     const int nc = (sm == MAD_GAUSS_SEIDEL && !fused) ? c_->ncolors : 1;
     REQUIRE(sm != MAD_GAUSS_SEIDEL_LEX, MAD_ERR_UNSUPPORTED, "bench of the lexicographic mode");
     const unsigned nl = n * nc;
-    std::vector<hipEvent_t> ev(2 * nl);
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    hipEvent_t a, z;
-    HIP_CHECK(hipEventCreate(&a));
-    HIP_CHECK(hipEventCreate(&z));
+    std::vector<Event> ev(2 * nl);
+    Event a, z;
     HIP_CHECK(hipEventRecord(a, c_->stream));
     const int rows = (nc == 4) ? (L.g.ny + 1) / 2 : L.g.ny;
     unsigned q = 0;
@@ -2474,37 +2384,24 @@ class Solver final : public SolverBase {
     }
     HIP_CHECK(hipEventRecord(z, c_->stream));
     HIP_CHECK(hipEventSynchronize(z));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, a, z));
     double ksum = 0.0;
     launch_ms.assign(q, 0.f);
     for (unsigned i = 0; i < q; ++i) {
-      float km = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&km, ev[2 * i], ev[2 * i + 1]));
-      ksum += km;
-      launch_ms[i] = km;
+      launch_ms[i] = elapsed(ev[2 * i], ev[2 * i + 1]);
+      ksum += launch_ms[i];
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(z);
-    *total_ms = ms;
+    *total_ms = elapsed(a, z);
     *kern_ms = q ? ksum / q : 0.0;
     *launches = q;
   }
 
   void bench_vcycle(unsigned n, double* total_ms) override {
-    hipEvent_t a, z;
-    HIP_CHECK(hipEventCreate(&a));
-    HIP_CHECK(hipEventCreate(&z));
+    Event a, z;
     HIP_CHECK(hipEventRecord(a, c_->stream));
     for (unsigned s = 0; s < n; ++s) vcycle_fast();
     HIP_CHECK(hipEventRecord(z, c_->stream));
     HIP_CHECK(hipEventSynchronize(z));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, a, z));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(z);
-    *total_ms = ms;
+    *total_ms = elapsed(a, z);
   }
 
  private:

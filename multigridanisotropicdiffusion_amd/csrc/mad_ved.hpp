@@ -505,12 +505,6 @@ void ved_tensor_any(mad_ved_ctx* v) {
   else ved_tensor_impl<float>(v);
 }
 
-float elapsed(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-  return ms;
-}
-
 // this rank's z-slab of level 0: [z0, z1) planes, element offset and count
 struct VedSlab {
   int64_t off, n;
@@ -532,8 +526,7 @@ void ved_run_impl(mad_ved_ctx* v, const void* in, int in_dt, void* out, int out_
   REQUIRE(dist || c->d.nranks == 1, MAD_ERR_STATE, "nranks > 1 needs mad_ved_comm_init first");
   const VedSlab sl = ved_slab(v);
   ved_load_image(v, in, in_dt, dev);
-  hipEvent_t ev[4];
-  for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+  Event ev[3];
   double tensor_ms = 0.0, diff_ms = 0.0, relres = 0.0;
   unsigned cycles = 0;
   int stalled = 0;
@@ -559,7 +552,6 @@ void ved_run_impl(mad_ved_ctx* v, const void* in, int in_dt, void* out, int out_
     relres = ms.last_relres;
     stalled |= ms.stalled;
   }
-  for (auto& e : ev) HIP_CHECK(hipEventDestroy(e));
   // static_cast of this rank's slab to the output pixel type (VED.hxx:139-150)
   void* dst = dev ? out : ved_stage(v, oes * sl.n);
   convert_from<double>(v->img + sl.off, dst, out_dt, sl.n, c->stream);

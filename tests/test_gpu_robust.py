@@ -79,6 +79,35 @@ def test_nan_tensor_raises_numeric(prec):
     assert e.value.code == M.capi.ERR_NUMERIC
 
 
+@pytest.mark.parametrize("prec", ["FP32", "FP64", "FP32_REFINE"])
+def test_failed_run_leaves_no_trace_recording(prec):
+    """A run that ends in MAD_ERR_NUMERIC leaves the benchmark trace switched off: a kernel-API
+    V-cycle on the same context afterwards records nothing (it used to append 2 nu + 1 entries)."""
+    import multigridanisotropicdiffusion_amd as M
+    shape = (20, 22, 24)
+    T = synth.random_spd(shape, seed=1)
+    good = synth.image(shape, seed=2)
+    bad = good.copy()
+    bad[5, 6, 7] = np.nan
+    kw = dict(time_step=0.3, precision=getattr(M, prec), options=M.capi.OPT_BENCHMARK_TRACE)
+    s = M.Solver(shape, **kw)
+    s.set_tensor(T)
+    with pytest.raises(M.capi.MadError) as e:
+        s.run(bad)
+    assert e.value.code == M.capi.ERR_NUMERIC
+    s.upload(0, M.capi.X, good)
+    s.upload(0, M.capi.B, good)
+    s.vcycle()
+    assert len(s.cycle_trace()) == 0
+    s.close()
+    # control: a run that succeeds still records its 2 nu + 1 entries per V-cycle
+    s = M.Solver(shape, **kw)
+    s.set_tensor(T)
+    _, st = s.run(good)
+    assert st["total_cycles"] > 0 and len(s.cycle_trace()) == 5 * st["total_cycles"]
+    s.close()
+
+
 def test_zero_image_is_not_numeric_error():
     import multigridanisotropicdiffusion_amd as M
     shape = (16, 18, 20)
