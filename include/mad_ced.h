@@ -1,0 +1,106 @@
+/*
+ * mad_ced.h -- C ABI of the structure-tensor diffusion filters on the GPU: Weickert's
+ * edge-enhancing (EED) and coherence-enhancing (CED) diffusion, a sibling of the VED
+ * pipeline of mad_ved.h.  The diffusion tensor is derived from the image's smoothed
+ * structure tensor on the device and handed to the MAD solver of mad.h in place.
+ *
+ * Definition (3D, image u, spacing h, borders replicated by index clamping, x fastest;
+ * K0 / K1 the sampled Gaussian / first-derivative taps of mad_ved.h's FIR operator,
+ * radius max(1, ceil(4 s / h_d)) for a physical scale s on axis d):
+ *   1. gradient at the noise scale sigma: g_d = K1(sigma) along d, K0(sigma) along the
+ *      other two axes (passes z, y, x; correlation sum_t K(t) f(clamp(i + t))), times 1 / h_d
+ *   2. products J0 = [gx gx, gx gy, gx gz, gy gy, gy gz, gz gz]
+ *   3. integration at the feature scale rho: K0(rho) along x, y, z of each component
+ *      (the clamp acts on J0)
+ *   4. eigen-analysis of J_rho: mu0 <= mu1 <= mu2, orthonormal v_i
+ *   5. with h(d) = exp(-(K^2 / d)^m) for d > 0 and 0 otherwise (contrast K, exponent m):
+ *        EED: lambda_i = 1 - (1 - alpha) h(mu_i - mu0)
+ *        CED: lambda_i = alpha + (1 - alpha) h(mu2 - mu_i)
+ *   6. D = sum_i lambda_i v_i v_i^T, fp64 SoA [xx,xy,xz,yy,yz,zz]
+ * Outer loop as in VED: per iteration one tensor generation from the current image, then
+ * diffusion_iterations implicit steps of time_step through the MAD solver.
+ * See DESIGN.md "Structure-tensor diffusion" and tests/ced_numpy.py.
+ */
+#ifndef MAD_CED_H
+#define MAD_CED_H
+
+#include "mad.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef enum mad_ced_enhancement {
+  MAD_CED_EED = 0,                 /* edge enhancing: smooths along edges, not across */
+  MAD_CED_CED = 1                  /* coherence enhancing: smooths along the coherence direction */
+} mad_ced_enhancement;
+
+typedef struct mad_ced_desc {
+  uint32_t abi_version;            /* MAD_ABI_VERSION */
+  int64_t size[3];                 /* x, y, z (3D only) */
+  double spacing[3];               /* image spacing, x first */
+  int32_t enhancement;             /* mad_ced_enhancement, MAD_CED_EED */
+  double noise_scale;              /* sigma, physical units, 0.5 */
+  double feature_scale;            /* rho, physical units, 2.0 */
+  double contrast;                 /* K, 1.0 */
+  double exponent;                 /* m, 2.0 */
+  double alpha;                    /* 0 < alpha < 1, 0.01 */
+  uint32_t iterations;             /* 1  (outer iterations: tensor generation + diffusion) */
+  uint32_t diffusion_iterations;   /* 5  (MAD NumberOfSteps per iteration) */
+  /* MAD parameters of the diffusion steps (MaxCycles fixed at 100, as in VED) */
+  int32_t cycle;                   /* MAD_VCYCLE */
+  double time_step;                /* 0.1 */
+  double tolerance;                /* 1e-6 */
+  uint32_t diffusion_iterations_per_grid; /* 2 */
+  int32_t smoother;                /* mad_smoother, MAD_GAUSS_SEIDEL */
+  int32_t precision;               /* MAD_PRECISION_AUTO (default) / MAD_FP32 / MAD_FP32_REFINE: fp32
+                                      passes, the diffusion solve as mad_create resolves it;
+                                      MAD_FP64: fp64 throughout.  The eigen-analysis and the
+                                      eigenvalue map run in fp64 in every mode. */
+  int32_t device;                  /* HIP device, -1 = current */
+  int32_t verbose;                 /* 0 */
+  uint32_t options;                /* reserved, 0 */
+  int32_t reserved[5];
+} mad_ced_desc;
+
+typedef struct mad_ced_stats {
+  uint32_t iterations;             /* outer iterations run */
+  uint32_t total_cycles;           /* MAD cycles over all iterations and steps */
+  double last_relres;              /* relative residual at the end of the last step */
+  double tensor_ms;                /* device time of the tensor generations, all iterations */
+  double diffusion_ms;             /* MAD setup + solve, all iterations */
+  double pass_ms[5];               /* device time per pass (z, y, x + products, rho y, rho z +
+                                      eigen), summed over the iterations */
+  int32_t stalled;                 /* any step ended by the fp32 stall guard */
+  int32_t reserved[7];
+} mad_ced_stats;
+
+typedef struct mad_ced_ctx mad_ced_ctx;
+
+int mad_ced_desc_init(mad_ced_desc *d);
+int mad_ced_create(const mad_ced_desc *d, mad_ced_ctx **out);
+void mad_ced_destroy(mad_ced_ctx *ctx);
+const char *mad_ced_last_error(const mad_ced_ctx *ctx);
+
+/* The whole filter: host image in (any mad_dtype, x fastest), host image out (static_cast,
+ * i.e. truncation for integer types).  MAD_ERR_NOT_CONVERGED (output written) when the stall
+ * guard ended a diffusion step above the tolerance, as mad_ved_run.  Single GPU. */
+int mad_ced_run(mad_ced_ctx *ctx, const void *in, int32_t in_dtype, void *out,
+                int32_t out_dtype, mad_ced_stats *stats);
+/* same with device buffers */
+int mad_ced_run_device(mad_ced_ctx *ctx, const void *in, int32_t in_dtype, void *out,
+                       int32_t out_dtype, mad_ced_stats *stats);
+
+/* One tensor generation on a host image (parity / inspection).  tensor_soa: 6 arrays of N
+ * doubles [xx,xy,xz,yy,yz,zz]; lambda_soa (may be NULL): 3 arrays of N doubles, the mapped
+ * eigenvalues in the order of the ascending structure-tensor eigenvalues. */
+int mad_ced_tensor(mad_ced_ctx *ctx, const void *image, int32_t dtype, double *tensor_soa,
+                   double *lambda_soa);
+/* Steps 1-3 on a host image: J_rho, 6 arrays of N doubles. */
+int mad_ced_structure_tensor(mad_ced_ctx *ctx, const void *image, int32_t dtype,
+                             double *structure_soa);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

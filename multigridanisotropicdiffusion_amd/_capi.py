@@ -38,6 +38,8 @@ OPT_BENCHMARK_TRACE = 16  # the reference's -DBENCHMARK history in mad_get_cycle
 OPT_NO_PLACEMENT_TUNE = 32  # keep level 0's first allocation (mad_placement_trials)
 OPT_NO_RECORD_B = 64  # SMOOTHER: level-0 records without b (the split-b sweep instead)
 VED_OPT_LINE_WALK = 1
+# mad_ced_enhancement (include/mad_ced.h)
+CED_EED, CED_CED = 0, 1
 
 EXPORTS = (
     "mad_desc_init", "mad_max_depth", "mad_create", "mad_destroy", "mad_last_error",
@@ -57,6 +59,12 @@ EXPORTS = (
     "mad_ved_run", "mad_ved_run_device", "mad_ved_comm_init", "mad_ved_comm_init_local",
     "mad_ved_comm_init_solo",
     "mad_ved_tensor", "mad_ved_hessian",
+)
+
+# include/mad_ced.h (kept apart: EXPORTS is the function set of mad.h + mad_ved.h)
+CED_EXPORTS = (
+    "mad_ced_desc_init", "mad_ced_create", "mad_ced_destroy", "mad_ced_last_error",
+    "mad_ced_run", "mad_ced_run_device", "mad_ced_tensor", "mad_ced_structure_tensor",
 )
 
 VED_MAX_SCALES = 16
@@ -159,6 +167,51 @@ class VedStats(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
 
 
+class CedDesc(ctypes.Structure):
+    """mad_ced_desc (include/mad_ced.h)."""
+    _fields_ = [
+        ("abi_version", ctypes.c_uint32),
+        ("size", ctypes.c_int64 * 3),
+        ("spacing", ctypes.c_double * 3),
+        ("enhancement", ctypes.c_int32),
+        ("noise_scale", ctypes.c_double),
+        ("feature_scale", ctypes.c_double),
+        ("contrast", ctypes.c_double),
+        ("exponent", ctypes.c_double),
+        ("alpha", ctypes.c_double),
+        ("iterations", ctypes.c_uint32),
+        ("diffusion_iterations", ctypes.c_uint32),
+        ("cycle", ctypes.c_int32),
+        ("time_step", ctypes.c_double),
+        ("tolerance", ctypes.c_double),
+        ("diffusion_iterations_per_grid", ctypes.c_uint32),
+        ("smoother", ctypes.c_int32),
+        ("precision", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("verbose", ctypes.c_int32),
+        ("options", ctypes.c_uint32),
+        ("reserved", ctypes.c_int32 * 5),
+    ]
+
+
+class CedStats(ctypes.Structure):
+    _fields_ = [
+        ("iterations", ctypes.c_uint32),
+        ("total_cycles", ctypes.c_uint32),
+        ("last_relres", ctypes.c_double),
+        ("tensor_ms", ctypes.c_double),
+        ("diffusion_ms", ctypes.c_double),
+        ("pass_ms", ctypes.c_double * 5),
+        ("stalled", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 7),
+    ]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("reserved", "pass_ms")}
+        d["pass_ms"] = list(self.pass_ms)
+        return d
+
+
 class MadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mad error {code}: {msg}")
@@ -246,6 +299,14 @@ def load():
         "mad_ved_comm_init_solo": ([vp], i32),
         "mad_ved_tensor": ([vp, vp, i32, dp, dp], i32),
         "mad_ved_hessian": ([vp, vp, i32, dbl, dp], i32),
+        "mad_ced_desc_init": ([ctypes.POINTER(CedDesc)], i32),
+        "mad_ced_create": ([ctypes.POINTER(CedDesc), ctypes.POINTER(vp)], i32),
+        "mad_ced_destroy": ([vp], None),
+        "mad_ced_last_error": ([vp], ctypes.c_char_p),
+        "mad_ced_run": ([vp, vp, i32, vp, i32, ctypes.POINTER(CedStats)], i32),
+        "mad_ced_run_device": ([vp, vp, i32, vp, i32, ctypes.POINTER(CedStats)], i32),
+        "mad_ced_tensor": ([vp, vp, i32, dp, dp], i32),
+        "mad_ced_structure_tensor": ([vp, vp, i32, dp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
