@@ -20,6 +20,25 @@
  * Outer loop as in VED: per iteration one tensor generation from the current image, then
  * diffusion_iterations implicit steps of time_step through the MAD solver.
  * See DESIGN.md "Structure-tensor diffusion" and tests/ced_numpy.py.
+ *
+ * 2D (mad_ced_desc.dim == 2, image u(y, x), spacing (hx, hy), size[2] == 1): the same
+ * definition minus the z axis, computed by one fused kernel per tensor generation.
+ *   1. gx = K1x(K0y u) / hx, gy = K0x(K1y u) / hy (pass along y first, then x)
+ *   2. J0 = [gx gx, gx gy, gy gy]
+ *   3. J_rho = K0y(rho)(K0x(rho) J0): x first, then y; the x clamp acts on J0, the y clamp
+ *      on the x-smoothed products
+ *   4. with J_rho = [[a, b], [b, c]]: m = (a + c) / 2, d = (a - c) / 2, r = hypot(d, b),
+ *      mu0 = m - r, mu1 = m + r; mu1 - mu0 is taken as 2 r, never as a difference
+ *   5. EED: lambda0 = 1, lambda1 = 1 - (1 - alpha) h(2 r)
+ *      CED: lambda0 = alpha + (1 - alpha) h(2 r), lambda1 = alpha
+ *   6. D = s I + q [[d, b], [b, -d]], s = (lambda0 + lambda1) / 2,
+ *      q = (lambda1 - lambda0) / (2 r) for r > 0, else 0 (= sum_i lambda_i v_i v_i^T without
+ *      eigenvectors, continuous at r = 0); fp64 SoA [xx,xy,yy]
+ * Steps 4-6 run in fp64 in every precision mode.  mad_ced_tensor then writes 3 arrays
+ * [xx,xy,yy] and 2 lambda arrays (lambda0, lambda1: the order of the ascending mu),
+ * mad_ced_structure_tensor 3 arrays; mad_ced_run / mad_ced_run_device behave as in 3D.
+ * mad_ced_stats.pass_ms[0] carries the fused kernel's time, entries 1-4 are 0.
+ * See DESIGN.md "Structure-tensor diffusion, 2D" and tests/ced2d_numpy.py.
  */
 #ifndef MAD_CED_H
 #define MAD_CED_H
@@ -37,8 +56,8 @@ typedef enum mad_ced_enhancement {
 
 typedef struct mad_ced_desc {
   uint32_t abi_version;            /* MAD_ABI_VERSION */
-  int64_t size[3];                 /* x, y, z (3D only) */
-  double spacing[3];               /* image spacing, x first */
+  int64_t size[3];                 /* x, y, z (dim 2: z = 1) */
+  double spacing[3];               /* image spacing, x first (dim 2: spacing[2] is ignored) */
   int32_t enhancement;             /* mad_ced_enhancement, MAD_CED_EED */
   double noise_scale;              /* sigma, physical units, 0.5 */
   double feature_scale;            /* rho, physical units, 2.0 */
@@ -60,7 +79,9 @@ typedef struct mad_ced_desc {
   int32_t device;                  /* HIP device, -1 = current */
   int32_t verbose;                 /* 0 */
   uint32_t options;                /* reserved, 0 */
-  int32_t reserved[5];
+  int32_t dim;                     /* 3 (default; 0 is read as 3, the value a caller built before
+                                      this field existed passes) or 2; anything else is invalid */
+  int32_t reserved[4];
 } mad_ced_desc;
 
 typedef struct mad_ced_stats {
@@ -70,9 +91,11 @@ typedef struct mad_ced_stats {
   double tensor_ms;                /* device time of the tensor generations, all iterations */
   double diffusion_ms;             /* MAD setup + solve, all iterations */
   double pass_ms[5];               /* device time per pass (z, y, x + products, rho y, rho z +
-                                      eigen), summed over the iterations */
+                                      eigen), summed over the iterations; dim 2: [0] is the fused
+                                      kernel, [1..4] are 0 */
   int32_t stalled;                 /* any step ended by the fp32 stall guard */
-  int32_t reserved[7];
+  int32_t tile[2];                 /* dim 2: the fused kernel's output tile (x, y); 0 in 3D */
+  int32_t reserved[5];
 } mad_ced_stats;
 
 typedef struct mad_ced_ctx mad_ced_ctx;
@@ -93,10 +116,11 @@ int mad_ced_run_device(mad_ced_ctx *ctx, const void *in, int32_t in_dtype, void 
 
 /* One tensor generation on a host image (parity / inspection).  tensor_soa: 6 arrays of N
  * doubles [xx,xy,xz,yy,yz,zz]; lambda_soa (may be NULL): 3 arrays of N doubles, the mapped
- * eigenvalues in the order of the ascending structure-tensor eigenvalues. */
+ * eigenvalues in the order of the ascending structure-tensor eigenvalues.  dim 2: 3 arrays
+ * [xx,xy,yy] and 2 lambda arrays. */
 int mad_ced_tensor(mad_ced_ctx *ctx, const void *image, int32_t dtype, double *tensor_soa,
                    double *lambda_soa);
-/* Steps 1-3 on a host image: J_rho, 6 arrays of N doubles. */
+/* Steps 1-3 on a host image: J_rho, 6 arrays of N doubles (dim 2: 3 arrays). */
 int mad_ced_structure_tensor(mad_ced_ctx *ctx, const void *image, int32_t dtype,
                              double *structure_soa);
 

@@ -7,6 +7,9 @@
 //     include/mad/itkMultigridGaussSeidelSmoother.h, itkMultigridWeightedJacobiSmoother.h
 //   itk::VEDMultigridImageFilter<TIn, TOut, TSmoother>
 //     include/itkVEDMultigridImageFilter.h:43-168 (through mad_ved.h)
+//   mad::CoherenceEnhancingDiffusionImageFilter<TIn, TOut, TSmoother>
+//     structure-tensor EED / CED, 2D or 3D (through mad_ced.h; the setter names of ITK's
+//     AnisotropicDiffusionLBR filter of that name)
 // ITK itself is not a dependency: images are the small mad::itkshim::Image below
 // (buffer + size + spacing + origin, x fastest, region index 0).  With a real
 // ITK build the same class body sits behind itk::ImageToImageFilter: GenerateData
@@ -26,6 +29,7 @@
 #include <vector>
 
 #include "mad.h"
+#include "mad_ced.h"
 #include "mad_ved.h"
 
 namespace mad {
@@ -310,6 +314,89 @@ class VEDMultigridImageFilter {
   mad_ved_desc desc_{};
   mad_ved_ctx* ctx_ = nullptr;
   mad_ved_stats stats_{};
+  bool converged_ = true;
+  const TInputImage* input_ = nullptr;
+  typename TOutputImage::Pointer output_;
+};
+
+// Structure-tensor diffusion (Weickert's EED / CED, mad_ced.h): the tensor comes from the image
+// itself, so there is no SetDiffusionTensor.  Templated on the dimension like ITK's
+// CoherenceEnhancingDiffusionImageFilter: a 2D image takes the fused 2D tensor kernel
+// (mad_ced_desc.dim = 2), a 3D image the five passes.
+template <class TInputImage, class TOutputImage,
+          class TSmootherType = MultigridGaussSeidelSmoother<TInputImage::ImageDimension>>
+class CoherenceEnhancingDiffusionImageFilter {
+ public:
+  static constexpr unsigned int Dim = TInputImage::ImageDimension;
+  static_assert(Dim == 2 || Dim == 3, "structure-tensor diffusion is 2D or 3D");
+  static_assert(TOutputImage::ImageDimension == Dim, "input and output dimensions differ");
+  using Self = CoherenceEnhancingDiffusionImageFilter;
+  using Pointer = std::shared_ptr<Self>;
+  using InputPixelType = typename TInputImage::PixelType;
+  using OutputPixelType = typename TOutputImage::PixelType;
+  using Precision = double;
+  enum CycleType { VCYCLE = MAD_VCYCLE, FMG = MAD_FMG, SMOOTHER = MAD_SMOOTHER };
+  enum EnhancementType { EED = MAD_CED_EED, CED = MAD_CED_CED };
+
+  static Pointer New() { return Pointer(new Self()); }
+  ~CoherenceEnhancingDiffusionImageFilter() { mad_ced_destroy(ctx_); }
+
+  void SetEnhancement(EnhancementType e) { desc_.enhancement = e; }
+  void SetNoiseScale(Precision v) { desc_.noise_scale = v; }
+  void SetFeatureScale(Precision v) { desc_.feature_scale = v; }
+  void SetContrast(Precision v) { desc_.contrast = v; }
+  void SetExponent(Precision v) { desc_.exponent = v; }
+  void SetAlpha(Precision v) { desc_.alpha = v; }
+  void SetIterations(unsigned int n) { desc_.iterations = n; }
+  void SetDiffusionIterations(unsigned int n) { desc_.diffusion_iterations = n; }
+  void SetCycle(CycleType c) { desc_.cycle = c; }
+  void SetTimeStep(Precision dt) { desc_.time_step = dt; }
+  void SetTolerance(Precision t) { desc_.tolerance = t; }
+  void SetDiffusionIterationsPerGrid(unsigned int n) { desc_.diffusion_iterations_per_grid = n; }
+  void SetVerbose(bool v) { desc_.verbose = v ? 1 : 0; }
+  // MI355X execution options
+  void SetPrecision(int32_t p) { desc_.precision = p; }
+  void SetDevice(int32_t d) { desc_.device = d; }
+
+  const mad_ced_desc& GetDescriptor() const { return desc_; }
+  void SetInput(const TInputImage* img) { input_ = img; }
+  typename TOutputImage::Pointer GetOutput() const { return output_; }
+  const mad_ced_stats& GetStats() const { return stats_; }
+
+  void Update() {
+    if (!input_) throw Error(MAD_ERR_STATE, "SetInput first");
+    mad_ced_desc d = desc_;
+    d.dim = (int32_t)Dim;
+    for (unsigned q = 0; q < 3; ++q) {
+      d.size[q] = q < Dim ? input_->GetSize()[q] : 1;
+      d.spacing[q] = q < Dim ? input_->GetSpacing()[q] : 1.0;
+    }
+    d.smoother = TSmootherType::id;
+    mad_ced_destroy(ctx_);
+    ctx_ = nullptr;
+    if (int rc = mad_ced_create(&d, &ctx_))
+      throw Error(rc, std::string("mad_ced: ") + mad_ced_last_error(nullptr));
+    output_ = TOutputImage::New();
+    output_->SetRegions(input_->GetSize());
+    output_->Allocate();
+    output_->SetSpacing(input_->GetSpacing());
+    output_->SetOrigin(input_->GetOrigin());
+    const int rc = mad_ced_run(ctx_, input_->GetBufferPointer(), itkshim::PixelTraits<InputPixelType>::id,
+                               output_->GetBufferPointer(), itkshim::PixelTraits<OutputPixelType>::id,
+                               &stats_);
+    converged_ = check_run(rc, "mad_ced", mad_ced_last_error(ctx_));
+  }
+  bool GetConverged() const { return converged_; }
+
+ protected:
+  CoherenceEnhancingDiffusionImageFilter() {
+    if (int rc = mad_ced_desc_init(&desc_)) throw Error(rc, "mad_ced_desc_init");
+  }
+
+ private:
+  mad_ced_desc desc_{};
+  mad_ced_ctx* ctx_ = nullptr;
+  mad_ced_stats stats_{};
   bool converged_ = true;
   const TInputImage* input_ = nullptr;
   typename TOutputImage::Pointer output_;

@@ -13,7 +13,7 @@ from .filters import (Image, MultigridAnisotropicDiffusionImageFilter,
                       MultigridWeightedJacobiSmoother, TensorImage)
 from .solver import Solver, comm_unique_id, max_depth, slab_range
 from .ved import VED, VEDMultigridImageFilter
-from .ced import CED, CoherenceEnhancingDiffusionImageFilter
+from .ced import CED, CED2D, CoherenceEnhancingDiffusionImageFilter
 from . import mhd
 
 __all__ = [
@@ -22,5 +22,5 @@ __all__ = [
     "MultigridGaussSeidelLexSmoother", "MultigridWeightedJacobiSmoother", "MadError",
     "VCYCLE", "FMG", "SMOOTHER", "GAUSS_SEIDEL", "GAUSS_SEIDEL_LEX", "WEIGHTED_JACOBI",
     "FP32", "FP32_REFINE", "FP64", "PRECISION_AUTO", "NotConvergedWarning", "VED", "VEDMultigridImageFilter", "mhd",
-    "CED", "CoherenceEnhancingDiffusionImageFilter",
+    "CED", "CED2D", "CoherenceEnhancingDiffusionImageFilter",
 ]

@@ -190,7 +190,8 @@ class CedDesc(ctypes.Structure):
         ("device", ctypes.c_int32),
         ("verbose", ctypes.c_int32),
         ("options", ctypes.c_uint32),
-        ("reserved", ctypes.c_int32 * 5),
+        ("dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 4),
     ]
 
 
@@ -203,12 +204,14 @@ class CedStats(ctypes.Structure):
         ("diffusion_ms", ctypes.c_double),
         ("pass_ms", ctypes.c_double * 5),
         ("stalled", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 7),
+        ("tile", ctypes.c_int32 * 2),
+        ("reserved", ctypes.c_int32 * 5),
     ]
 
     def as_dict(self):
-        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("reserved", "pass_ms")}
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("reserved", "pass_ms", "tile")}
         d["pass_ms"] = list(self.pass_ms)
+        d["tile"] = tuple(self.tile)
         return d
 
 

@@ -7,8 +7,9 @@ eigenvalue map that keeps diffusion along edges / coherent structures and damps 
 them (definition: include/mad_ced.h).  Everything -- the five tensor passes and the MAD
 diffusion steps -- runs in libmad_hip.so; there is no CPU fallback.
 
-``CED`` is the low-level context (one image size); ``CoherenceEnhancingDiffusionImageFilter``
-the ITK-shaped facade (the setters ITK users know from the AnisotropicDiffusionLBR module).
+``CED`` is the low-level context (one image size) for volumes, ``CED2D`` the same for 2D
+images (one fused tensor kernel); ``CoherenceEnhancingDiffusionImageFilter`` the ITK-shaped
+facade (the setters ITK users know from the AnisotropicDiffusionLBR module).
 """
 import ctypes
 
@@ -30,25 +31,30 @@ def _enhancement(v):
     return int(v)
 
 
-class CED:
-    """One mad_ced_ctx.  shape: numpy (z, y, x); spacing x first.  enhancement: "eed" /
-    "ced" (or C.CED_EED / C.CED_CED)."""
+class _Context:
+    """One mad_ced_ctx of dimension DIM (the body CED and CED2D share).  shape: numpy, x last;
+    spacing x first.  enhancement: "eed" / "ced" (or C.CED_EED / C.CED_CED)."""
 
-    def __init__(self, shape, spacing=(1.0, 1.0, 1.0), *, enhancement="eed", noise_scale=0.5,
+    DIM = None
+
+    def __init__(self, shape, spacing=None, *, enhancement="eed", noise_scale=0.5,
                  feature_scale=2.0, contrast=1.0, exponent=2.0, alpha=0.01, iterations=1,
                  diffusion_iterations=5, cycle=C.VCYCLE, time_step=0.1, tolerance=1e-6,
                  diffusion_iterations_per_grid=2, verbose=False, smoother=C.GAUSS_SEIDEL,
                  precision=C.PRECISION_AUTO, device=-1):
-        if len(shape) != 3:
-            raise ValueError("structure-tensor diffusion is 3D only")
+        dim = self.DIM
+        if len(shape) != dim:
+            raise ValueError(f"{type(self).__name__} takes a {dim}D shape (CED: volumes, CED2D: images)")
         self._L = C.load()
         self.shape = tuple(int(v) for v in shape)
+        self.ncomp = dim * (dim + 1) // 2
         d = C.CedDesc()
         C.check(self._L.mad_ced_desc_init(ctypes.byref(d)))
+        d.dim = dim
         for q, n in enumerate(reversed(self.shape)):
             d.size[q] = n
-        for q in range(3):
-            d.spacing[q] = float(spacing[q])
+        for q in range(dim):
+            d.spacing[q] = float(spacing[q]) if spacing is not None else 1.0
         d.enhancement = _enhancement(enhancement)
         d.noise_scale, d.feature_scale = float(noise_scale), float(feature_scale)
         d.contrast, d.exponent, d.alpha = float(contrast), float(exponent), float(alpha)
@@ -96,11 +102,11 @@ class CED:
         return out, stats
 
     def tensor(self, image, with_lambda=False):
-        """One tensor generation: SoA tensor (6, z, y, x) [xx,xy,xz,yy,yz,zz]; with_lambda:
-        (tensor, the three mapped eigenvalues (3, z, y, x))."""
+        """One tensor generation: SoA tensor (6, z, y, x) [xx,xy,xz,yy,yz,zz] or (3, y, x)
+        [xx,xy,yy]; with_lambda: (tensor, the mapped eigenvalues (3, z, y, x) / (2, y, x))."""
         img = self._img(image)
-        T = np.empty((6,) + self.shape)
-        lam = np.empty((3,) + self.shape) if with_lambda else None
+        T = np.empty((self.ncomp,) + self.shape)
+        lam = np.empty((self.DIM,) + self.shape) if with_lambda else None
         dp = ctypes.POINTER(ctypes.c_double)
         self._check(self._L.mad_ced_tensor(self._ctx, img.ctypes.data_as(ctypes.c_void_p),
                                            mad_dtype(img.dtype), T.ctypes.data_as(dp),
@@ -108,13 +114,25 @@ class CED:
         return (T, lam) if with_lambda else T
 
     def structure_tensor(self, image):
-        """The smoothed structure tensor J_rho: (6, z, y, x), [xx,xy,xz,yy,yz,zz]."""
+        """The smoothed structure tensor J_rho: (6, z, y, x) [xx,xy,xz,yy,yz,zz] or (3, y, x)
+        [xx,xy,yy]."""
         img = self._img(image)
-        J = np.empty((6,) + self.shape)
+        J = np.empty((self.ncomp,) + self.shape)
         self._check(self._L.mad_ced_structure_tensor(
             self._ctx, img.ctypes.data_as(ctypes.c_void_p), mad_dtype(img.dtype),
             J.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return J
+
+
+class CED(_Context):
+    """The 3D context.  shape: numpy (z, y, x); spacing (hx, hy, hz)."""
+    DIM = 3
+
+
+class CED2D(_Context):
+    """The 2D context (mad_ced_desc.dim = 2).  shape: numpy (y, x); spacing (hx, hy); tensor
+    (3, y, x) [xx,xy,yy], the mapped eigenvalues (2, y, x)."""
+    DIM = 2
 
 
 class CoherenceEnhancingDiffusionImageFilter:
@@ -165,12 +183,14 @@ class CoherenceEnhancingDiffusionImageFilter:
 
     def Update(self):
         """Run the filter on the GPU; the output pixel type is the input's unless
-        output_dtype was given; spacing and origin carry over."""
+        output_dtype was given; spacing and origin carry over.  The input's dimension picks
+        the 2D or the 3D context (ITK's filter is templated on it)."""
         if self._input is None:
             raise RuntimeError("SetInput must be called before Update")
         img = self._input
         out_dtype = self._output_dtype or img.array.dtype
-        v = CED(img.array.shape, img.spacing, smoother=self._smoother.smoother_id,
+        ctx = CED2D if img.dim == 2 else CED
+        v = ctx(img.array.shape, img.spacing, smoother=self._smoother.smoother_id,
                 precision=self._precision, device=self._device, **self._p)
         try:
             out, stats = v.run(img.array, out_dtype=out_dtype)

@@ -9,12 +9,14 @@ struct mad_ced_ctx {
   mad_ced_desc d{};
   std::string err;
   mad_ctx* mad = nullptr;  // the diffusion solver, kept across iterations
+  int dim = 3;             // 2: the fused kernel ced2_k, tensor [xx,xy,yy]
+  int tile[2] = {0, 0};    // 2D: the output tile of the last tensor generation (x, y)
   int64_t n[3] = {0, 0, 0};
   int64_t N = 0;
   double* img = nullptr;   // internal image (fp64)
   double* img2 = nullptr;  // next iterate
   void* vol = nullptr;     // 12 scratch volumes in the storage precision
-  void* taps = nullptr;    // device taps, per axis [K0(sigma) | K1(sigma) | K0(rho)]
+  void* taps = nullptr;    // device taps, per axis [K0(sigma) | K1(sigma) | K0(rho)] (2D: K0(rho) zero-padded)
   int Rs[3] = {0, 0, 0}, Rr[3] = {0, 0, 0};
   size_t tap_off[3] = {0, 0, 0};  // element offset of each axis' taps
   double* lam = nullptr;   // mapped eigenvalues, SoA x3 (mad_ced_tensor only)
@@ -87,19 +89,32 @@ void ced_lds_attr() {
   done = true;
 }
 
+template <typename T>
+void ced2_lds_attr() {
+  static bool done = false;
+  if (done) return;
+  for (const void* k : {(const void*)ced2_k<T, CED_TENSOR>, (const void*)ced2_k<T, CED_STRUCTURE>})
+    HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVedLds));
+  done = true;
+}
+
 // the taps of both scales on every axis (ved_taps: the VED FIR operator's K0, K1), in the
-// storage precision, uploaded once: the scales are fixed for the context's lifetime
+// storage precision, uploaded once: the scales are fixed for the context's lifetime.  2D: three
+// zeros on either side of K0(rho), for ced2_k's four-outputs-per-thread rho phases.
 template <typename T>
 void ced_upload_taps(mad_ced_ctx* v) {
   std::vector<T> kt;
-  for (int q = 0; q < 3; ++q) {
+  const int pad = v->dim == 2 ? 3 : 0;
+  for (int q = 0; q < v->dim; ++q) {
     std::vector<double> Ks, Kr;
     v->Rs[q] = ved_taps(v->d.noise_scale, v->d.spacing[q], Ks);
     v->Rr[q] = ved_taps(v->d.feature_scale, v->d.spacing[q], Kr);
     const int Ws = 2 * v->Rs[q] + 1, Wr = 2 * v->Rr[q] + 1;
     v->tap_off[q] = kt.size();
     for (int t = 0; t < 2 * Ws; ++t) kt.push_back((T)Ks[t]);  // K0 | K1
+    kt.insert(kt.end(), pad, T(0));
     for (int t = 0; t < Wr; ++t) kt.push_back((T)Kr[t]);      // K0
+    kt.insert(kt.end(), pad, T(0));
   }
   HIP_CHECK(hipMalloc(&v->taps, sizeof(T) * kt.size()));
   HIP_CHECK(hipMemcpy(v->taps, kt.data(), sizeof(T) * kt.size(), hipMemcpyHostToDevice));
@@ -169,8 +184,68 @@ void ced_generate(mad_ced_ctx* v, int mode, double* D, int64_t cs, double* lam, 
   HIP_CHECK(hipGetLastError());
 }
 
+// The LDS regions of ced2_k for a TW x TH tile, in elements: R1 = image tile | three products
+// (column-major, pitch HB + 1), R2 = K0y u, K1y u | three x-smoothed products (row pitch TW + 1);
+// the kernel's comment names the phases.
+struct Ced2Lds {
+  int s1, s2;
+};
+Ced2Lds ced2_lds(int TW, int TH, const int* Rs, const int* Rr) {
+  const int WA = TW + 2 * (Rs[0] + Rr[0]), HA = TH + 2 * (Rs[1] + Rr[1]);
+  const int HB = TH + 2 * Rr[1], WC = TW + 2 * Rr[0];
+  return {std::max(WA * HA, 3 * WC * (HB + 1)), std::max(2 * WA * HB, 3 * HB * (TW + 1))};
+}
+
+// 2D: one tensor generation from v->img by the fused kernel.  ev: events around it (ev[0],
+// ev[1]; ev[2..5] follow at once so the 3D bookkeeping holds).
+template <typename T>
+void ced2_generate(mad_ced_ctx* v, int mode, double* D, int64_t cs, double* lam, Event* ev) {
+  hipStream_t st = v->mad->stream;
+  const int nx = (int)v->n[0], ny = (int)v->n[1];
+  const int* Rs = v->Rs;
+  const int* Rr = v->Rr;
+  auto bytes = [&](int TW, int TH) {
+    const Ced2Lds l = ced2_lds(TW, TH, Rs, Rr);
+    return ((size_t)l.s1 + l.s2) * sizeof(T);
+  };
+  // 64 x 32 outputs per block of 256 threads.  Rows are halved first (the x row stays one
+  // wave wide): down to 8 while that brings the block under half a CU's 160 KiB of LDS (two
+  // blocks per CU hide each other's barriers), then, rows before columns, as far as the taps
+  // need to fit at all.  Below 16 x 4 the halo is all of the tile's work.
+  int TW = 64, TH = 32;
+  while (TH > 8 && bytes(TW, TH) > 80 * 1024) TH /= 2;
+  while (TH > 4 && bytes(TW, TH) > kVedLds) TH /= 2;
+  while (TW > 16 && bytes(TW, TH) > kVedLds) TW /= 2;
+  const size_t lds = bytes(TW, TH);
+  REQUIRE(lds <= kVedLds, MAD_ERR_UNSUPPORTED,
+          "Gaussian taps too long for the LDS tiles (scale / spacing too large)");
+  v->tile[0] = TW;
+  v->tile[1] = TH;
+  ced2_lds_attr<T>();
+  const T* tp = (const T*)v->taps;
+  const double* h = v->d.spacing;
+  const CedParams cp{v->d.enhancement, v->d.contrast * v->d.contrast, v->d.exponent, v->d.alpha};
+  const dim3 grid((nx + TW - 1) / TW, (ny + TH - 1) / TH);
+  const int s1 = ced2_lds(TW, TH, Rs, Rr).s1;
+  if (ev) HIP_CHECK(hipEventRecord(ev[0], st));
+  if (mode == CED_STRUCTURE)
+    hipLaunchKernelGGL((ced2_k<T, CED_STRUCTURE>), grid, dim3(256), lds, st, v->img, tp + v->tap_off[0],
+                       tp + v->tap_off[1], Rs[0], Rs[1], Rr[0], Rr[1], nx, ny, TW, TH, s1, (T)(1.0 / h[0]),
+                       (T)(1.0 / h[1]), cs, D, nullptr, cp);
+  else
+    hipLaunchKernelGGL((ced2_k<T, CED_TENSOR>), grid, dim3(256), lds, st, v->img, tp + v->tap_off[0],
+                       tp + v->tap_off[1], Rs[0], Rs[1], Rr[0], Rr[1], nx, ny, TW, TH, s1, (T)(1.0 / h[0]),
+                       (T)(1.0 / h[1]), cs, D, lam, cp);
+  if (ev)
+    for (int q = 1; q < 6; ++q) HIP_CHECK(hipEventRecord(ev[q], st));
+  HIP_CHECK(hipGetLastError());
+}
+
 void ced_generate_any(mad_ced_ctx* v, int mode, double* D, int64_t cs, double* lam, Event* ev) {
-  if (v->d.precision == MAD_FP64) ced_generate<double>(v, mode, D, cs, lam, ev);
+  const bool f64 = v->d.precision == MAD_FP64;
+  if (v->dim == 2 && f64) ced2_generate<double>(v, mode, D, cs, lam, ev);
+  else if (v->dim == 2) ced2_generate<float>(v, mode, D, cs, lam, ev);
+  else if (f64) ced_generate<double>(v, mode, D, cs, lam, ev);
   else ced_generate<float>(v, mode, D, cs, lam, ev);
 }
 
@@ -202,7 +277,8 @@ void ced_run_impl(mad_ced_ctx* v, const void* in, int in_dt, void* out, int out_
     std::swap(v->img, v->img2);
     HIP_CHECK(hipEventRecord(done, c->stream));
     HIP_CHECK(hipEventSynchronize(done));
-    for (int q = 0; q < 5; ++q) pass_ms[q] += elapsed(ev[q], ev[q + 1]);
+    // 2D: the fused kernel is pass 0, the others stay 0
+    for (int q = 0; q < (v->dim == 2 ? 1 : 5); ++q) pass_ms[q] += elapsed(ev[q], ev[q + 1]);
     diff_ms += elapsed(ev[5], done);
     cycles += ms.total_cycles;
     relres = ms.last_relres;
@@ -223,6 +299,8 @@ void ced_run_impl(mad_ced_ctx* v, const void* in, int in_dt, void* out, int out_
     }
     st->diffusion_ms = diff_ms;
     st->stalled = stalled;
+    st->tile[0] = v->tile[0];
+    st->tile[1] = v->tile[1];
   }
 }
 
@@ -262,6 +340,7 @@ int mad_ced_desc_init(mad_ced_desc* d) {
   d->smoother = MAD_GAUSS_SEIDEL;
   d->precision = MAD_PRECISION_AUTO;
   d->device = -1;
+  d->dim = 3;
   return MAD_OK;
 }
 
@@ -280,15 +359,20 @@ int mad_ced_create(const mad_ced_desc* d, mad_ced_ctx** out) {
     REQUIRE(d->exponent > 0.0, MAD_ERR_INVALID, "exponent must be positive");
     REQUIRE(d->alpha > 0.0 && d->alpha < 1.0, MAD_ERR_INVALID, "alpha must lie in (0, 1)");
     REQUIRE(d->options == 0, MAD_ERR_INVALID, "unknown option bits");
-    for (int q = 0; q < 3; ++q)
+    // dim 0: a caller built against the header that had no dim there (reserved, zero)
+    const int dim = d->dim == 0 ? 3 : d->dim;
+    REQUIRE(dim == 2 || dim == 3, MAD_ERR_INVALID, "dim must be 2 or 3 (0 is read as 3)");
+    REQUIRE(dim == 3 || d->size[2] == 1, MAD_ERR_INVALID, "dim 2 needs size[2] == 1");
+    for (int q = 0; q < dim; ++q)
       REQUIRE(d->spacing[q] > 0.0, MAD_ERR_INVALID, "spacing must be positive");
     v->d = *d;
+    v->dim = dim;
     mad_desc md;
     mad_desc_init(&md);
-    md.dim = 3;
+    md.dim = dim;
     for (int q = 0; q < 3; ++q) {
       md.size[q] = d->size[q];
-      md.spacing[q] = d->spacing[q];
+      md.spacing[q] = q < dim ? d->spacing[q] : 1.0;
     }
     md.cycle = d->cycle;
     md.smoother = d->smoother;
@@ -345,13 +429,14 @@ int mad_ced_tensor(mad_ced_ctx* v, const void* image, int32_t dtype, double* ten
   return ced_guarded(v, [&] {
     HIP_CHECK(hipSetDevice(v->mad->device));
     ced_load_image(v, image, dtype, false);
-    if (lambda_soa && !v->lam) HIP_CHECK(big_alloc((void**)&v->lam, sizeof(double) * 3 * v->N));
+    const int nc = v->dim == 2 ? 3 : 6;  // tensor components; dim mapped eigenvalues
+    if (lambda_soa && !v->lam) HIP_CHECK(big_alloc((void**)&v->lam, sizeof(double) * v->dim * v->N));
     ced_tensor_to_solver(v, lambda_soa ? v->lam : nullptr, nullptr);
     hipStream_t st = v->mad->stream;
     // one rank: the solver's tensor is the whole grid, component stride N
-    HIP_CHECK(hipMemcpyAsync(tensor_soa, tensor_at0(v->mad), sizeof(double) * 6 * v->N, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(tensor_soa, tensor_at0(v->mad), sizeof(double) * nc * v->N, hipMemcpyDeviceToHost, st));
     if (lambda_soa)
-      HIP_CHECK(hipMemcpyAsync(lambda_soa, v->lam, sizeof(double) * 3 * v->N, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(lambda_soa, v->lam, sizeof(double) * v->dim * v->N, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
   });
 }
@@ -361,11 +446,12 @@ int mad_ced_structure_tensor(mad_ced_ctx* v, const void* image, int32_t dtype, d
   return ced_guarded(v, [&] {
     HIP_CHECK(hipSetDevice(v->mad->device));
     ced_load_image(v, image, dtype, false);
+    const int nc = v->dim == 2 ? 3 : 6;
     double* J = nullptr;
-    HIP_CHECK(big_alloc((void**)&J, sizeof(double) * 6 * v->N));
+    HIP_CHECK(big_alloc((void**)&J, sizeof(double) * nc * v->N));
     std::unique_ptr<double, void (*)(double*)> hold(J, [](double* p) { (void)hipFree(p); });
     ced_generate_any(v, CED_STRUCTURE, J, v->N, nullptr, nullptr);
-    HIP_CHECK(hipMemcpyAsync(structure_soa, J, sizeof(double) * 6 * v->N, hipMemcpyDeviceToHost,
+    HIP_CHECK(hipMemcpyAsync(structure_soa, J, sizeof(double) * nc * v->N, hipMemcpyDeviceToHost,
                              v->mad->stream));
     HIP_CHECK(hipStreamSynchronize(v->mad->stream));
   });

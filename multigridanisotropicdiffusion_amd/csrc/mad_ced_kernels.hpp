@@ -14,6 +14,7 @@
 //   5. ced_rz_k   six volumes         -> K0z(rho) of each = J_rho, then per voxel   6 T + 48
 //                 eigen-analysis, eigenvalue map, fp64 tensor (or J_rho itself)
 // Algorithmic traffic in fp32: 16 + 20 + 36 + 48 + 72 = 192 B per voxel.
+// 2D images take one fused kernel instead, ced2_k at the end of this file: 8 + 24 = 32 B per pixel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -344,6 +345,243 @@ __global__ void __launch_bounds__(256) ced_rz_k(CedVol6<const T> in, const T* __
     }
     ced_point<MODE>((double)s0, (double)s1, (double)s2, (double)s3, (double)s4, (double)s5,
                     (int64_t)(z0 + o) * sz + col, cs, D, lam, n, cp);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// 2D: one fused kernel per tensor generation (include/mad_ced.h "2D").  The sigma + rho halo
+// of a 2D tile fits LDS, so the image goes in and the fp64 tensor comes out with nothing in
+// between touching memory: 8 + 24 = 32 algorithmic bytes per pixel.
+
+// h(t) as ced_stop; the default exponent 2 (and 1) skips pow
+__device__ inline double ced2_stop(double t, const CedParams& cp) {
+#pragma clang fp contract(off)
+  if (!(t > 0.0)) return 0.0;
+  const double x = cp.k2 / t;
+  return exp(-(cp.m == 2.0 ? x * x : cp.m == 1.0 ? x : pow(x, cp.m)));
+}
+
+// floor(e / W) for 0 <= e < 2^20 from inv = 1.0f / W: (e + 0.5) / W is at least 0.5 / W away from
+// an integer, the two roundings move it by less than e / W * 2^-23
+__device__ __forceinline__ int ced2_div(int e, float inv) { return (int)(((float)e + 0.5f) * inv); }
+
+// one pixel: J_rho = [[a, b], [b, c]] out (CED_STRUCTURE), or the closed-form eigenvalues
+// mu = m -+ r, the eigenvalue map on mu1 - mu0 = 2 r, and D = s I + q [[d, b], [b, -d]]
+// (= sum lam_i v_i v_i^T without eigenvectors, continuous at r = 0); lam: optional two
+// arrays of the mapped eigenvalues, stride n.  fp64 in every mode.
+template <int MODE>
+__device__ __forceinline__ void ced2_point(double a, double b, double c, int64_t p, int64_t cs,
+                                           double* __restrict__ D, double* __restrict__ lam,
+                                           int64_t n, const CedParams& cp) {
+#pragma clang fp contract(off)
+  if (MODE == CED_STRUCTURE) {
+    D[p] = a;
+    D[cs + p] = b;
+    D[2 * cs + p] = c;
+    return;
+  }
+  const double d = 0.5 * (a - c);
+  const double r = hypot(d, b);
+  const double h = (1.0 - cp.alpha) * ced2_stop(2.0 * r, cp);
+  double l0, l1;
+  if (cp.enhancement == 0) {
+    l0 = 1.0;
+    l1 = 1.0 - h;
+  } else {
+    l0 = cp.alpha + h;
+    l1 = cp.alpha;
+  }
+  const double s = 0.5 * (l0 + l1);
+  const double q = r > 0.0 ? (l1 - l0) / (2.0 * r) : 0.0;
+  const double qd = q * d;
+  D[p] = s + qd;
+  D[cs + p] = q * b;
+  D[2 * cs + p] = s - qd;
+  if (lam) {
+    lam[p] = l0;
+    lam[n + p] = l1;
+  }
+}
+
+// Block = 256 threads, a TW x TH output tile at (x0, y0); TW a power of two, TH a multiple of 4.
+// With H = Rs + Rr per axis, LDS holds two regions that the phases use in turn (S1 = the size of
+// the first in elements, from the host):
+//   A  R1  image tile (TW + 2 Hx) x (TH + 2 Hy), clamped, fp64 -> T
+//   B  R2  K0y u, K1y u at the rows clamp(y0 - Rr_y + rb), rb < HB = TH + 2 Rr_y, all staged columns
+//   C  R1  gx gx, gx gy, gy gy at the columns clamp(x0 - Rr_x + m) of those rows (A is dead),
+//          stored column-major with the odd pitch HB + 1
+//   D  R2  K0x(rho) of the three on the TW tile columns, same rows, row pitch TW + 1 (B is dead)
+//   E       K0y(rho) in registers, ced2_point, store
+// A halo position outside the image holds the value AT THE CLAMPED POSITION (each pass's clamp
+// acts on the previous pass's output, as in the 3D kernels).  Every LDS index is tile-relative
+// and built from a clamped coordinate p with x0 - Rr <= p <= x0 + TW - 1 + Rr (the tile starts
+// inside the image), so p +- Rs stays inside the staged range for any image size.
+// A thread works on four outputs at a time, so one uniform tap load serves eight (B, C) or
+// twelve (D, E) fma, their LDS reads are in flight together and the index arithmetic is paid
+// once per four.  In B and C the four are the same column of four rows.  In D and E they are
+// consecutive along the filtered axis and share their input reads (W + 3 reads for 4 outputs
+// instead of 4 W): output j takes input r with the tap r - j, read from a tap row padded with
+// three zeros on either side, so each output still sums its taps t = -R..R in order and the
+// zero taps add nothing.  With the column-major products a wave's lanes run along the rows in
+// D and along x in E: both read consecutive addresses, and the odd pitches keep C's and D's
+// transposing stores off a single bank.
+// taps_x / taps_y: [K0(sigma) | K1(sigma) | 0 0 0 K0(rho) 0 0 0] of the axis.
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) ced2_k(const double* __restrict__ in, const T* __restrict__ taps_x,
+                                              const T* __restrict__ taps_y, int Rsx, int Rsy, int Rrx,
+                                              int Rry, int nx, int ny, int TW, int TH, int S1, T ihx,
+                                              T ihy, int64_t cs, double* __restrict__ D,
+                                              double* __restrict__ lam, CedParams cp) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char ved_smem[];
+  T* R1 = reinterpret_cast<T*>(ved_smem);
+  T* R2 = R1 + S1;
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+  const int Hx = Rsx + Rrx, Hy = Rsy + Rry;
+  const int WA = TW + 2 * Hx, HA = TH + 2 * Hy;  // staged image
+  const int HB = TH + 2 * Rry;                   // rows of phases B, C, D
+  const int WC = TW + 2 * Rrx;                   // columns of phase C
+  const int PC = HB + 1, PD = TW + 1;            // pitches of C (per column) and D (per row)
+  const int Wsx = 2 * Rsx + 1, Wsy = 2 * Rsy + 1, Wrx = 2 * Rrx + 1, Wry = 2 * Rry + 1;
+  const float iWA = 1.0f / (float)WA, iWC = 1.0f / (float)WC;
+  // A: eight loads in flight per thread
+  const int nA = WA * HA;
+  for (int e0 = tid; e0 < nA; e0 += 2048) {
+    double u[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int e = min(e0 + 256 * j, nA - 1);
+      const int r = ced2_div(e, iWA), c = e - r * WA;
+      const int yy = min(max(y0 - Hy + r, 0), ny - 1), xx = min(max(x0 - Hx + c, 0), nx - 1);
+      u[j] = in[(int64_t)yy * nx + xx];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (e0 + 256 * j < nA) R1[e0 + 256 * j] = (T)u[j];
+  }
+  __syncthreads();
+  // B: item = (staged column c, rows 4 g .. 4 g + 3); lanes run along c
+  const int nB = WA * HB, GB = (HB + 3) / 4;
+  for (int e = tid; e < WA * GB; e += 256) {
+    const int g = ced2_div(e, iWA), c = e - g * WA;
+    const T* a[4];
+    T b0[4], b1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int p = min(max(y0 - Rry + min(4 * g + j, HB - 1), 0), ny - 1);
+      a[j] = R1 + (p - Rsy - (y0 - Hy)) * WA + c;
+      b0[j] = b1[j] = T(0);
+    }
+#pragma unroll 2
+    for (int q = 0; q < Wsy; ++q) {
+      const T k0 = taps_y[q], k1 = taps_y[Wsy + q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const T v = a[j][q * WA];
+        b0[j] = fma(k0, v, b0[j]);
+        b1[j] = fma(k1, v, b1[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * g + j < HB) {
+        R2[(4 * g + j) * WA + c] = b0[j];
+        R2[nB + (4 * g + j) * WA + c] = b1[j];
+      }
+  }
+  __syncthreads();
+  // C: item = (product column m, rows 4 g .. 4 g + 3); lanes run along m
+  const int SC = WC * PC;
+  for (int e = tid; e < WC * GB; e += 256) {
+    const int g = ced2_div(e, iWC), m = e - g * WC;
+    const int p = min(max(x0 - Rrx + m, 0), nx - 1);
+    const T* b[4];
+    T gx[4], gy[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      b[j] = R2 + min(4 * g + j, HB - 1) * WA + (p - Rsx - (x0 - Hx));
+      gx[j] = gy[j] = T(0);
+    }
+#pragma unroll 2
+    for (int q = 0; q < Wsx; ++q) {
+      const T k0 = taps_x[q], k1 = taps_x[Wsx + q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        gx[j] = fma(k1, b[j][q], gx[j]);
+        gy[j] = fma(k0, b[j][nB + q], gy[j]);
+      }
+    }
+    T* o = R1 + m * PC + 4 * g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * g + j < HB) {
+        const T x = gx[j] * ihx, y = gy[j] * ihy;
+        o[j] = x * x;
+        o[SC + j] = x * y;
+        o[2 * SC + j] = y * y;
+      }
+  }
+  __syncthreads();
+  // D: item = (row rb, four consecutive tile columns i0..i0+3); lanes run along rb
+  const int SD = HB * PD;
+  const T* krx = taps_x + 2 * Wsx;  // the padded rho taps: tap t at [3 + t]
+  const float iHB = 1.0f / (float)HB;
+  for (int e = tid; e < HB * (TW / 4); e += 256) {
+    const int g = ced2_div(e, iHB), rb = e - g * HB, i0 = 4 * g;
+    const T* c = R1 + i0 * PC + rb;
+    T s[3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[a][j] = T(0);
+#pragma unroll 2
+    for (int r = 0; r < Wrx + 3; ++r) {
+      const T v0 = c[r * PC], v1 = c[SC + r * PC], v2 = c[2 * SC + r * PC];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const T kr = krx[3 + r - j];
+        s[0][j] = fma(kr, v0, s[0][j]);
+        s[1][j] = fma(kr, v1, s[1][j]);
+        s[2][j] = fma(kr, v2, s[2][j]);
+      }
+    }
+    T* o = R2 + rb * PD + i0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[a * SD + j] = s[a][j];
+  }
+  __syncthreads();
+  // E: item = (tile column xi, four consecutive rows o..o+3); lanes run along x
+  const int yend = min(TH, ny - y0);
+  const T* kry = taps_y + 2 * Wsy;
+  const int64_t n = (int64_t)nx * ny;
+  for (int e = tid; e < TW * (TH / 4); e += 256) {
+    const int xi = e & (TW - 1), o = 4 * (e / TW), i = x0 + xi;
+    if (i >= nx) continue;
+    const T* c = R2 + o * PD + xi;
+    T s[3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[a][j] = T(0);
+#pragma unroll 2
+    for (int r = 0; r < Wry + 3; ++r) {
+      const T v0 = c[r * PD], v1 = c[SD + r * PD], v2 = c[2 * SD + r * PD];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const T kr = kry[3 + r - j];
+        s[0][j] = fma(kr, v0, s[0][j]);
+        s[1][j] = fma(kr, v1, s[1][j]);
+        s[2][j] = fma(kr, v2, s[2][j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (o + j < yend)
+        ced2_point<MODE>((double)s[0][j], (double)s[1][j], (double)s[2][j], (int64_t)(y0 + o + j) * nx + i, cs,
+                         D, lam, n, cp);
   }
 }
 
