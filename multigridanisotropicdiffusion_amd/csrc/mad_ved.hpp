@@ -19,6 +19,7 @@ struct mad_ved_ctx {
   void* fir = nullptr;     // 9 FIR volumes in the storage precision
   double* iir = nullptr;   // 12 volumes (T) of the recursive Hessian passes
   void* taps = nullptr;    // per-axis taps of the current scale (device)
+  double* off = nullptr;   // fp32 FIR: the constant taken off the image (ved_offset_k)
   double* resp = nullptr;  // m_MaxVesselnessResponse
   double* dir = nullptr;   // vessel direction (eigenvector column 2 of the max scale), SoA x3
   void* stage = nullptr;   // host <-> device staging
@@ -28,7 +29,7 @@ struct mad_ved_ctx {
   ~mad_ved_ctx() {
     if (mad) (void)hipSetDevice(mad->device);
     if (mad && mad->stream) (void)hipStreamSynchronize(mad->stream);
-    for (void* p : {(void*)img, (void*)img2, fir, (void*)iir, taps, (void*)resp, (void*)dir, stage, xbuf})
+    for (void* p : {(void*)img, (void*)img2, fir, (void*)iir, taps, (void*)off, (void*)resp, (void*)dir, stage, xbuf})
       if (p) (void)hipFree(p);
     if (mad) mad_destroy(mad);
   }
@@ -427,14 +428,25 @@ void ved_scale(mad_ved_ctx* v, double sigma, int mode, bool first, double* hess,
   hipStream_t st = v->mad->stream;
   const int nx = (int)v->n[0], ny = (int)v->n[1], nz = (int)v->n[2];
   const int64_t N = v->N;
+  std::vector<double> K[3];
+  int R[3];
+  for (int q = 0; q < 3; ++q) R[q] = ved_taps(sigma, v->d.spacing[q], K[q]);
+  // LDS-staged passes: z tiles of ZT planes, y tiles of YT rows (smaller when the taps
+  // are long), x rows of 256
+  auto lds_for = [](int lines, int width, int copies) { return (size_t)lines * width * copies * sizeof(T); };
+  int ZT = 32, YT = 32;
+  while (ZT > 4 && lds_for(ZT + 2 * R[2], 256, 1) > kVedLds) ZT /= 2;
+  while (YT > 4 && lds_for(YT + 2 * R[1], 64, 3) > kVedLds) YT /= 2;
+  const size_t lz = lds_for(ZT + 2 * R[2], 256, 1), ly = lds_for(YT + 2 * R[1], 64, 3);
+  const size_t lx = lds_for(256 + 2 * R[0], 1, 6);
+  // refused before anything is allocated or copied
+  REQUIRE(lz <= kVedLds && ly <= kVedLds && lx <= kVedLds, MAD_ERR_UNSUPPORTED,
+          "Gaussian taps too long for the LDS tiles (sigma / spacing > ~18)");
   if (!v->fir) HIP_CHECK(big_alloc((void**)&v->fir, sizeof(T) * 9 * N));
   T* f = (T*)v->fir;
   T *z0 = f, *z1 = f + N, *z2 = f + 2 * N;
   T *a00 = f + 3 * N, *a10 = f + 4 * N, *a20 = f + 5 * N, *a01 = f + 6 * N, *a11 = f + 7 * N,
     *a02 = f + 8 * N;
-  std::vector<double> K[3];
-  int R[3];
-  for (int q = 0; q < 3; ++q) R[q] = ved_taps(sigma, v->d.spacing[q], K[q]);
   const size_t W[3] = {K[0].size(), K[1].size(), K[2].size()};
   std::vector<T> kt;
   for (int q = 0; q < 3; ++q)
@@ -446,19 +458,13 @@ void ved_scale(mad_ved_ctx* v, double sigma, int mode, bool first, double* hess,
   const T* tx = (const T*)v->taps;
   const T* ty = tx + W[0];
   const T* tz = ty + W[1];
-  // LDS-staged passes: z tiles of ZT planes, y tiles of YT rows (smaller when the taps
-  // are long), x rows of 256
-  auto lds_for = [](int lines, int width, int copies) { return (size_t)lines * width * copies * sizeof(T); };
-  int ZT = 32, YT = 32;
-  while (ZT > 4 && lds_for(ZT + 2 * R[2], 256, 1) > kVedLds) ZT /= 2;
-  while (YT > 4 && lds_for(YT + 2 * R[1], 64, 3) > kVedLds) YT /= 2;
-  const size_t lz = lds_for(ZT + 2 * R[2], 256, 1), ly = lds_for(YT + 2 * R[1], 64, 3);
-  const size_t lx = lds_for(256 + 2 * R[0], 1, 6);
-  REQUIRE(lz <= kVedLds && ly <= kVedLds && lx <= kVedLds, MAD_ERR_UNSUPPORTED,
-          "Gaussian taps too long for the LDS tiles (sigma / spacing > ~18)");
   ved_lds_attr<T>();
+  if (sizeof(T) == 4) {
+    if (!v->off) HIP_CHECK(hipMalloc((void**)&v->off, sizeof(double)));
+    hipLaunchKernelGGL(ved_offset_k, dim3(1), dim3(256), 0, st, v->img, N, v->off);
+  }
   hipLaunchKernelGGL((ved_fir_z_k<T>), dim3((nx + 63) / 64, (ny + 3) / 4, (nz + ZT - 1) / ZT),
-                     dim3(256), lz, st, v->img, z0, z1, z2, tz, R[2], nx, ny, nz, ZT);
+                     dim3(256), lz, st, v->img, z0, z1, z2, tz, R[2], nx, ny, nz, ZT, v->off);
   hipLaunchKernelGGL((ved_fir_y_k<T>), dim3((nx + 63) / 64, (ny + YT - 1) / YT, nz), dim3(256), ly,
                      st, z0, z1, z2, a00, a10, a20, a01, a11, a02, ty, R[1], nx, ny, nz, YT);
   const dim3 gr((nx + 255) / 256, ny, nz);
@@ -722,11 +728,16 @@ int mad_ved_hessian(mad_ved_ctx* v, const void* image, int32_t dtype, double sig
     ved_load_image(v, image, dtype, false);
     double* H = nullptr;
     HIP_CHECK(big_alloc((void**)&H, sizeof(double) * 6 * v->N));
-    if (v->d.precision == MAD_FP64) ved_scale<double>(v, sigma, VED_HESSIAN, true, H);
-    else ved_scale<float>(v, sigma, VED_HESSIAN, true, H);
-    HIP_CHECK(hipMemcpyAsync(hessian_soa, H, sizeof(double) * 6 * v->N, hipMemcpyDeviceToHost,
-                             v->mad->stream));
-    HIP_CHECK(hipStreamSynchronize(v->mad->stream));
+    try {
+      if (v->d.precision == MAD_FP64) ved_scale<double>(v, sigma, VED_HESSIAN, true, H);
+      else ved_scale<float>(v, sigma, VED_HESSIAN, true, H);
+      HIP_CHECK(hipMemcpyAsync(hessian_soa, H, sizeof(double) * 6 * v->N, hipMemcpyDeviceToHost,
+                               v->mad->stream));
+      HIP_CHECK(hipStreamSynchronize(v->mad->stream));
+    } catch (...) {  // a refused scale (MAD_ERR_UNSUPPORTED) must not keep the buffer
+      (void)hipFree(H);
+      throw;
+    }
     HIP_CHECK(hipFree(H));
   });
 }
