@@ -21,6 +21,17 @@
  * diffusion_iterations implicit steps of time_step through the MAD solver.
  * See DESIGN.md "Structure-tensor diffusion" and tests/ced_numpy.py.
  *
+ * Limit on the scales (3D): every pass keeps its tile and the taps' halo in 128 KiB of LDS and
+ * shrinks the tile for long taps; taps that do not fit the smallest tile make
+ * mad_ced_run, mad_ced_tensor and mad_ced_structure_tensor return MAD_ERR_UNSUPPORTED
+ * ("Gaussian taps too long for the LDS tiles") before anything is launched; the context stays
+ * usable and is destroyed as usual.  The last pass sets the limit: it holds 4 + 2 R planes of
+ * six volumes over 64 columns, R = max(1, ceil(4 rho / h_z)) the radius of the feature scale
+ * along z, which fits for R <= 19 in MAD_FP64 (rho <= 4.75 h_z) and R <= 40 with fp32 storage
+ * (rho <= 10 h_z).  fp32 storage, the default precision, is the way past the fp64 limit.  The
+ * other passes allow more (fp64 / fp32 radii: sigma along z 30 / 62, sigma along y 62 / 126,
+ * rho along y 126 / 254).  2D has its own limit, DESIGN.md "Structure-tensor diffusion, 2D".
+ *
  * 2D (mad_ced_desc.dim == 2, image u(y, x), spacing (hx, hy), size[2] == 1): the same
  * definition minus the z axis, computed by one fused kernel per tensor generation.
  *   1. gx = K1x(K0y u) / hx, gy = K0x(K1y u) / hy (pass along y first, then x)
