@@ -2,7 +2,10 @@
 (several ranks as threads on one device; the RCCL path exchanges the same
 planes).  Distributed results must be BIT-identical to the single-rank run:
 ghost planes carry exactly the neighbour's values and every kernel evaluates
-the same arithmetic; only norm partial sums are re-associated across ranks."""
+the same arithmetic; only norm partial sums are re-associated across ranks.
+Every volume here has even sizes (even slab offsets and depths, one x tile);
+tests/test_gpu_slab_tiles.py makes the same bitwise claim, and compares with the
+oracle, at odd offsets and depths, ragged tiles, two colours and both hand-overs."""
 import numpy as np
 import pytest
 
