@@ -10,6 +10,9 @@
 //   mad::CoherenceEnhancingDiffusionImageFilter<TIn, TOut, TSmoother>
 //     structure-tensor EED / CED, 2D or 3D (through mad_ced.h; the setter names of ITK's
 //     AnisotropicDiffusionLBR filter of that name)
+//   mad::PeronaMalikDiffusionImageFilter<TIn, TOut, TSmoother>
+//     regularised Perona-Malik diffusion, 2D or 3D (through mad_pm.h; SetConductanceParameter /
+//     SetNumberOfIterations as in ITK's anisotropic-diffusion family)
 // ITK itself is not a dependency: images are the small mad::itkshim::Image below
 // (buffer + size + spacing + origin, x fastest, region index 0).  With a real
 // ITK build the same class body sits behind itk::ImageToImageFilter: GenerateData
@@ -30,6 +33,7 @@
 
 #include "mad.h"
 #include "mad_ced.h"
+#include "mad_pm.h"
 #include "mad_ved.h"
 
 namespace mad {
@@ -397,6 +401,96 @@ class CoherenceEnhancingDiffusionImageFilter {
   mad_ced_desc desc_{};
   mad_ced_ctx* ctx_ = nullptr;
   mad_ced_stats stats_{};
+  bool converged_ = true;
+  const TInputImage* input_ = nullptr;
+  typename TOutputImage::Pointer output_;
+};
+
+// Regularised Perona-Malik diffusion (mad_pm.h): D = g I with a scalar diffusivity of the
+// squared gradient at the noise scale.  Templated on the dimension like the filter above: a 2D
+// image takes the fused 2D tensor kernel (mad_pm_desc.dim = 2), a 3D image the three passes.
+// SetConductanceParameter / SetNumberOfIterations, the names of ITK's anisotropic-diffusion
+// family, are aliases of SetContrast / SetIterations; the implicit steps take time steps of
+// 1-10 where those explicit filters are capped near 0.06-0.125.
+template <class TInputImage, class TOutputImage,
+          class TSmootherType = MultigridGaussSeidelSmoother<TInputImage::ImageDimension>>
+class PeronaMalikDiffusionImageFilter {
+ public:
+  static constexpr unsigned int Dim = TInputImage::ImageDimension;
+  static_assert(Dim == 2 || Dim == 3, "Perona-Malik diffusion is 2D or 3D");
+  static_assert(TOutputImage::ImageDimension == Dim, "input and output dimensions differ");
+  using Self = PeronaMalikDiffusionImageFilter;
+  using Pointer = std::shared_ptr<Self>;
+  using InputPixelType = typename TInputImage::PixelType;
+  using OutputPixelType = typename TOutputImage::PixelType;
+  using Precision = double;
+  enum CycleType { VCYCLE = MAD_VCYCLE, FMG = MAD_FMG, SMOOTHER = MAD_SMOOTHER };
+  enum DiffusivityType {
+    WEICKERT = MAD_PM_WEICKERT,
+    EXPONENTIAL = MAD_PM_EXPONENTIAL,
+    RATIONAL = MAD_PM_RATIONAL
+  };
+
+  static Pointer New() { return Pointer(new Self()); }
+  ~PeronaMalikDiffusionImageFilter() { mad_pm_destroy(ctx_); }
+
+  void SetDiffusivity(DiffusivityType g) { desc_.diffusivity = g; }
+  void SetNoiseScale(Precision v) { desc_.noise_scale = v; }
+  void SetContrast(Precision v) { desc_.contrast = v; }
+  void SetConductanceParameter(Precision v) { SetContrast(v); }
+  void SetExponent(Precision v) { desc_.exponent = v; }
+  void SetAlpha(Precision v) { desc_.alpha = v; }
+  void SetIterations(unsigned int n) { desc_.iterations = n; }
+  void SetNumberOfIterations(unsigned int n) { SetIterations(n); }
+  void SetDiffusionIterations(unsigned int n) { desc_.diffusion_iterations = n; }
+  void SetCycle(CycleType c) { desc_.cycle = c; }
+  void SetTimeStep(Precision dt) { desc_.time_step = dt; }
+  void SetTolerance(Precision t) { desc_.tolerance = t; }
+  void SetDiffusionIterationsPerGrid(unsigned int n) { desc_.diffusion_iterations_per_grid = n; }
+  void SetVerbose(bool v) { desc_.verbose = v ? 1 : 0; }
+  // MI355X execution options
+  void SetPrecision(int32_t p) { desc_.precision = p; }
+  void SetDevice(int32_t d) { desc_.device = d; }
+
+  const mad_pm_desc& GetDescriptor() const { return desc_; }
+  void SetInput(const TInputImage* img) { input_ = img; }
+  typename TOutputImage::Pointer GetOutput() const { return output_; }
+  const mad_pm_stats& GetStats() const { return stats_; }
+
+  void Update() {
+    if (!input_) throw Error(MAD_ERR_STATE, "SetInput first");
+    mad_pm_desc d = desc_;
+    d.dim = (int32_t)Dim;
+    for (unsigned q = 0; q < 3; ++q) {
+      d.size[q] = q < Dim ? input_->GetSize()[q] : 1;
+      d.spacing[q] = q < Dim ? input_->GetSpacing()[q] : 1.0;
+    }
+    d.smoother = TSmootherType::id;
+    mad_pm_destroy(ctx_);
+    ctx_ = nullptr;
+    if (int rc = mad_pm_create(&d, &ctx_))
+      throw Error(rc, std::string("mad_pm: ") + mad_pm_last_error(nullptr));
+    output_ = TOutputImage::New();
+    output_->SetRegions(input_->GetSize());
+    output_->Allocate();
+    output_->SetSpacing(input_->GetSpacing());
+    output_->SetOrigin(input_->GetOrigin());
+    const int rc = mad_pm_run(ctx_, input_->GetBufferPointer(), itkshim::PixelTraits<InputPixelType>::id,
+                              output_->GetBufferPointer(), itkshim::PixelTraits<OutputPixelType>::id,
+                              &stats_);
+    converged_ = check_run(rc, "mad_pm", mad_pm_last_error(ctx_));
+  }
+  bool GetConverged() const { return converged_; }
+
+ protected:
+  PeronaMalikDiffusionImageFilter() {
+    if (int rc = mad_pm_desc_init(&desc_)) throw Error(rc, "mad_pm_desc_init");
+  }
+
+ private:
+  mad_pm_desc desc_{};
+  mad_pm_ctx* ctx_ = nullptr;
+  mad_pm_stats stats_{};
   bool converged_ = true;
   const TInputImage* input_ = nullptr;
   typename TOutputImage::Pointer output_;

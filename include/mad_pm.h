@@ -1,0 +1,136 @@
+/*
+ * mad_pm.h -- C ABI of regularised Perona-Malik (nonlinear isotropic) diffusion on the GPU:
+ * Perona and Malik's scalar diffusivity on Catte's pre-smoothed gradient, a sibling of the
+ * structure-tensor filters of mad_ced.h.  The diffusion tensor g I is derived from the image
+ * on the device and handed to the MAD solver of mad.h in place; the implicit steps are stable
+ * at time steps of 1-10, where explicit schemes are capped near 0.06-0.125.
+ *
+ * Definition (image u, spacing h, borders replicated by index clamping, x fastest; K0 / K1 the
+ * sampled Gaussian / first-derivative taps of mad_ved.h's FIR operator, radius
+ * max(1, ceil(4 sigma / h_d)) on axis d -- the operator of step 1 of mad_ced.h):
+ *   1. gradient at the noise scale sigma, exactly mad_ced.h's step 1:
+ *        3D: g_d = K1 along d, K0 along the other two axes (passes z, y, x; correlation
+ *            sum_t K(t) f(clamp(i + t))), times 1 / h_d once
+ *        2D: gx = K1x(K0y u) / hx, gy = K0x(K1y u) / hy (pass along y first, then x)
+ *   2. s = gx gx + gy gy (+ gz gz), summed left to right in the storage precision with
+ *      contraction off, then taken to fp64
+ *   3. diffusivity, fp64 in every precision mode (contrast K, exponent m, 0 < alpha < 1):
+ *        MAD_PM_WEICKERT     g0 = 1 - h(s), h(s) = exp(-(K^2 / s)^m) for s > 0, else 0 (the h
+ *                            of mad_ced.h: g is EED's across-edge eigenvalue wherever
+ *                            mu1 - mu0 = |grad u_sigma|^2)
+ *        MAD_PM_EXPONENTIAL  g0 = exp(-s / K^2)       (m is ignored)
+ *        MAD_PM_RATIONAL     g0 = 1 / (1 + s / K^2)   (m is ignored)
+ *      g = alpha + (1 - alpha) g0
+ *   4. D = g I, fp64 SoA [xx,xy,xz,yy,yz,zz] (2D: [xx,xy,yy]): the off-diagonals are exact
+ *      0.0, all diagonals hold the same bits
+ *   5. outer loop as in CED / VED: per iteration one tensor generation from the current image,
+ *      then diffusion_iterations implicit steps of time_step through the MAD solver
+ *      (MaxCycles fixed at 100).  The classic semi-implicit scheme is
+ *      diffusion_iterations = 1, iterations = n.
+ * See DESIGN.md "Nonlinear isotropic diffusion (Perona-Malik)" and tests/pm_numpy.py.
+ *
+ * Limit on sigma.  Every kernel keeps its tile and the taps' halo in 128 KiB of LDS and shrinks
+ * the tile for long taps; taps that do not fit the smallest tile make mad_pm_run,
+ * mad_pm_tensor and mad_pm_gradient return MAD_ERR_UNSUPPORTED ("Gaussian taps too long for
+ * the LDS tiles") before anything is launched; the context stays usable.
+ *   3D: the z and y passes are mad_ced.h's and set the limit: radius along z <= 30 in MAD_FP64
+ *       (sigma <= 7.5 h_z) and <= 62 with fp32 storage (sigma <= 15.5 h_z); along y <= 62 / 126.
+ *       The x pass (three rows of 256 + 2 R) allows far more.
+ *   2D: the fused kernel's smallest tile is 16 x 4; with R = (Rx, Ry) it needs
+ *       max((16 + 2 Rx)(4 + 2 Ry), 136) + 10 (16 + 2 Rx) elements, which fits for equal radii
+ *       R <= 56 in MAD_FP64 (sigma <= 14 h) and R <= 83 with fp32 storage (sigma <= 20.75 h).
+ * fp32 storage, the default precision, is the way past the fp64 limits.
+ *
+ * Monotonicity.  The MAD stencil discretises div(g grad u) as g lap u + grad g . grad u with
+ * central differences: the two neighbour weights along an axis are
+ * -dt / h^2 (g(p) +- (g(p + 1) - g(p - 1)) / 4).  Where |g(p + 1) - g(p - 1)| <= 4 g(p) they are
+ * non-positive and the implicit step obeys the maximum principle at any time step; a diffusivity
+ * that drops from 1 to alpha within two grid points (a small sigma and alpha with a contrast far
+ * below the edge's gradient) violates it, and the step then over- and undershoots at the edge.
+ * A noise scale of 1-2 grid spacings, the rational diffusivity, or a larger alpha keep it
+ * ("Monotonicity").
+ */
+#ifndef MAD_PM_H
+#define MAD_PM_H
+
+#include "mad.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef enum mad_pm_diffusivity {
+  MAD_PM_WEICKERT = 0,             /* 1 - exp(-(K^2 / s)^m): flat below K, a sharp drop above */
+  MAD_PM_EXPONENTIAL = 1,          /* exp(-s / K^2): Perona and Malik's first function */
+  MAD_PM_RATIONAL = 2              /* 1 / (1 + s / K^2): Perona and Malik's second function */
+} mad_pm_diffusivity;
+
+typedef struct mad_pm_desc {
+  uint32_t abi_version;            /* MAD_ABI_VERSION */
+  int64_t size[3];                 /* x, y, z (dim 2: z = 1) */
+  double spacing[3];               /* image spacing, x first (dim 2: spacing[2] is ignored) */
+  int32_t diffusivity;             /* mad_pm_diffusivity, MAD_PM_WEICKERT */
+  double noise_scale;              /* sigma, physical units, 0.5 */
+  double contrast;                 /* K, 1.0 */
+  double exponent;                 /* m, 2.0 (MAD_PM_WEICKERT only) */
+  double alpha;                    /* 0 < alpha < 1, 0.01 */
+  uint32_t iterations;             /* 1  (outer iterations: tensor generation + diffusion) */
+  uint32_t diffusion_iterations;   /* 5  (MAD NumberOfSteps per iteration) */
+  /* MAD parameters of the diffusion steps (MaxCycles fixed at 100, as in CED / VED) */
+  int32_t cycle;                   /* MAD_VCYCLE */
+  double time_step;                /* 0.1 */
+  double tolerance;                /* 1e-6 */
+  uint32_t diffusion_iterations_per_grid; /* 2 */
+  int32_t smoother;                /* mad_smoother, MAD_GAUSS_SEIDEL */
+  int32_t precision;               /* MAD_PRECISION_AUTO (default) / MAD_FP32 / MAD_FP32_REFINE: fp32
+                                      passes, the diffusion solve as mad_create resolves it;
+                                      MAD_FP64: fp64 throughout.  The diffusivity runs in fp64
+                                      in every mode. */
+  int32_t device;                  /* HIP device, -1 = current */
+  int32_t verbose;                 /* 0 */
+  uint32_t options;                /* reserved, 0 */
+  int32_t dim;                     /* 3 (default; 0 is read as 3) or 2; anything else is invalid */
+  int32_t reserved[4];
+} mad_pm_desc;
+
+typedef struct mad_pm_stats {
+  uint32_t iterations;             /* outer iterations run */
+  uint32_t total_cycles;           /* MAD cycles over all iterations and steps */
+  double last_relres;              /* relative residual at the end of the last step */
+  double tensor_ms;                /* device time of the tensor generations, all iterations */
+  double diffusion_ms;             /* MAD setup + solve, all iterations */
+  double pass_ms[3];               /* device time per pass (z, y, x + map), summed over the
+                                      iterations; dim 2: [0] is the fused kernel, [1..2] are 0 */
+  int32_t stalled;                 /* any step ended by the fp32 stall guard */
+  int32_t tile[2];                 /* dim 2: the fused kernel's output tile (x, y); 0 in 3D */
+  int32_t reserved[5];
+} mad_pm_stats;
+
+typedef struct mad_pm_ctx mad_pm_ctx;
+
+int mad_pm_desc_init(mad_pm_desc *d);
+int mad_pm_create(const mad_pm_desc *d, mad_pm_ctx **out);
+void mad_pm_destroy(mad_pm_ctx *ctx);
+const char *mad_pm_last_error(const mad_pm_ctx *ctx);
+
+/* The whole filter: host image in (any mad_dtype, x fastest), host image out (static_cast,
+ * i.e. truncation for integer types).  MAD_ERR_NOT_CONVERGED (output written) when the stall
+ * guard ended a diffusion step above the tolerance, as mad_ced_run.  Single GPU. */
+int mad_pm_run(mad_pm_ctx *ctx, const void *in, int32_t in_dtype, void *out, int32_t out_dtype,
+               mad_pm_stats *stats);
+/* same with device buffers */
+int mad_pm_run_device(mad_pm_ctx *ctx, const void *in, int32_t in_dtype, void *out,
+                      int32_t out_dtype, mad_pm_stats *stats);
+
+/* One tensor generation on a host image (parity / inspection).  tensor_soa: 6 arrays of N
+ * doubles [xx,xy,xz,yy,yz,zz] (dim 2: 3 arrays [xx,xy,yy]); diffusivity (may be NULL): N
+ * doubles, g itself. */
+int mad_pm_tensor(mad_pm_ctx *ctx, const void *image, int32_t dtype, double *tensor_soa,
+                  double *diffusivity);
+/* Step 1 on a host image: dim arrays of N doubles, (gx, gy, gz) or (gx, gy). */
+int mad_pm_gradient(mad_pm_ctx *ctx, const void *image, int32_t dtype, double *grad_soa);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -14,6 +14,7 @@ from .filters import (Image, MultigridAnisotropicDiffusionImageFilter,
 from .solver import Solver, comm_unique_id, max_depth, slab_range
 from .ved import VED, VEDMultigridImageFilter
 from .ced import CED, CED2D, CoherenceEnhancingDiffusionImageFilter
+from .pm import PM, PM2D, PeronaMalikDiffusionImageFilter
 from . import mhd
 
 __all__ = [
@@ -23,4 +24,5 @@ __all__ = [
     "VCYCLE", "FMG", "SMOOTHER", "GAUSS_SEIDEL", "GAUSS_SEIDEL_LEX", "WEIGHTED_JACOBI",
     "FP32", "FP32_REFINE", "FP64", "PRECISION_AUTO", "NotConvergedWarning", "VED", "VEDMultigridImageFilter", "mhd",
     "CED", "CED2D", "CoherenceEnhancingDiffusionImageFilter",
+    "PM", "PM2D", "PeronaMalikDiffusionImageFilter",
 ]

@@ -40,6 +40,8 @@ OPT_NO_RECORD_B = 64  # SMOOTHER: level-0 records without b (the split-b sweep i
 VED_OPT_LINE_WALK = 1
 # mad_ced_enhancement (include/mad_ced.h)
 CED_EED, CED_CED = 0, 1
+# mad_pm_diffusivity (include/mad_pm.h)
+PM_WEICKERT, PM_EXPONENTIAL, PM_RATIONAL = 0, 1, 2
 
 EXPORTS = (
     "mad_desc_init", "mad_max_depth", "mad_create", "mad_destroy", "mad_last_error",
@@ -65,6 +67,12 @@ EXPORTS = (
 CED_EXPORTS = (
     "mad_ced_desc_init", "mad_ced_create", "mad_ced_destroy", "mad_ced_last_error",
     "mad_ced_run", "mad_ced_run_device", "mad_ced_tensor", "mad_ced_structure_tensor",
+)
+
+# include/mad_pm.h (kept apart as well)
+PM_EXPORTS = (
+    "mad_pm_desc_init", "mad_pm_create", "mad_pm_destroy", "mad_pm_last_error",
+    "mad_pm_run", "mad_pm_run_device", "mad_pm_tensor", "mad_pm_gradient",
 )
 
 VED_MAX_SCALES = 16
@@ -215,6 +223,53 @@ class CedStats(ctypes.Structure):
         return d
 
 
+class PmDesc(ctypes.Structure):
+    """mad_pm_desc (include/mad_pm.h)."""
+    _fields_ = [
+        ("abi_version", ctypes.c_uint32),
+        ("size", ctypes.c_int64 * 3),
+        ("spacing", ctypes.c_double * 3),
+        ("diffusivity", ctypes.c_int32),
+        ("noise_scale", ctypes.c_double),
+        ("contrast", ctypes.c_double),
+        ("exponent", ctypes.c_double),
+        ("alpha", ctypes.c_double),
+        ("iterations", ctypes.c_uint32),
+        ("diffusion_iterations", ctypes.c_uint32),
+        ("cycle", ctypes.c_int32),
+        ("time_step", ctypes.c_double),
+        ("tolerance", ctypes.c_double),
+        ("diffusion_iterations_per_grid", ctypes.c_uint32),
+        ("smoother", ctypes.c_int32),
+        ("precision", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("verbose", ctypes.c_int32),
+        ("options", ctypes.c_uint32),
+        ("dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+class PmStats(ctypes.Structure):
+    _fields_ = [
+        ("iterations", ctypes.c_uint32),
+        ("total_cycles", ctypes.c_uint32),
+        ("last_relres", ctypes.c_double),
+        ("tensor_ms", ctypes.c_double),
+        ("diffusion_ms", ctypes.c_double),
+        ("pass_ms", ctypes.c_double * 3),
+        ("stalled", ctypes.c_int32),
+        ("tile", ctypes.c_int32 * 2),
+        ("reserved", ctypes.c_int32 * 5),
+    ]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("reserved", "pass_ms", "tile")}
+        d["pass_ms"] = list(self.pass_ms)
+        d["tile"] = tuple(self.tile)
+        return d
+
+
 class MadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mad error {code}: {msg}")
@@ -310,6 +365,14 @@ def load():
         "mad_ced_run_device": ([vp, vp, i32, vp, i32, ctypes.POINTER(CedStats)], i32),
         "mad_ced_tensor": ([vp, vp, i32, dp, dp], i32),
         "mad_ced_structure_tensor": ([vp, vp, i32, dp], i32),
+        "mad_pm_desc_init": ([ctypes.POINTER(PmDesc)], i32),
+        "mad_pm_create": ([ctypes.POINTER(PmDesc), ctypes.POINTER(vp)], i32),
+        "mad_pm_destroy": ([vp], None),
+        "mad_pm_last_error": ([vp], ctypes.c_char_p),
+        "mad_pm_run": ([vp, vp, i32, vp, i32, ctypes.POINTER(PmStats)], i32),
+        "mad_pm_run_device": ([vp, vp, i32, vp, i32, ctypes.POINTER(PmStats)], i32),
+        "mad_pm_tensor": ([vp, vp, i32, dp, dp], i32),
+        "mad_pm_gradient": ([vp, vp, i32, dp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmad_hip.so")
 SOURCES = ["mad_solver.hip"]
-DEPS = ["../../include/mad.h", "../../include/mad_ved.h", "../../include/mad_ced.h"]
+DEPS = ["../../include/mad.h", "../../include/mad_ved.h", "../../include/mad_ced.h",
+        "../../include/mad_pm.h"]
 
 
 def deps():

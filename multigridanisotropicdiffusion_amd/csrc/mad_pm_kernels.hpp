@@ -1,0 +1,254 @@
+// mad_pm_kernels.hpp -- device kernels of the regularised Perona-Malik tensor
+// (include/mad_pm.h): the gradient at the noise scale, its squared magnitude and a pointwise
+// diffusivity, D = g I.
+//
+// 3D: the gradient passes of the structure-tensor filter plus one new pass.  Storage and FIR
+// arithmetic in T (fp32, or fp64 in MAD_FP64) with explicit fma and contraction off; the
+// diffusivity and the tensor are fp64 in every mode.
+//   1. ced_z_k    image (fp64)        -> K0z u, K1z u                               8 + 2 T
+//   2. ced_y_k    those two           -> K0y K0z u, K1y K0z u, K0y K1z u            2 T + 3 T
+//   3. pm_x_k     those three         -> gradient (LDS and registers only), s, g,   3 T + 48
+//                 the six tensor components
+// Algorithmic traffic in fp32: 16 + 20 + 60 = 96 B per voxel (EED / CED: 192).
+// 2D images take one fused kernel, pm2_k at the end of this file: 8 + 24 = 32 B per pixel.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mad_ced_kernels.hpp"
+
+namespace mad {
+
+struct PmParams {
+  int diffusivity;  // MAD_PM_WEICKERT / MAD_PM_EXPONENTIAL / MAD_PM_RATIONAL
+  double k2;        // contrast^2
+  double m;         // exponent (Weickert only)
+  double alpha;
+};
+
+enum { PM_TENSOR = 0, PM_GRADIENT = 1 };
+
+// g(s) = alpha + (1 - alpha) g0(s), fp64; the default exponent 2 (and 1) skips pow, as ced2_stop
+__device__ inline double pm_diffusivity(double s, const PmParams& pp) {
+#pragma clang fp contract(off)
+  double g0;
+  if (pp.diffusivity == 0) {
+    if (s > 0.0) {
+      const double x = pp.k2 / s;
+      g0 = 1.0 - exp(-(pp.m == 2.0 ? x * x : pp.m == 1.0 ? x : pow(x, pp.m)));
+    } else {
+      g0 = 1.0;
+    }
+  } else if (pp.diffusivity == 1) {
+    g0 = exp(-(s / pp.k2));
+  } else {
+    g0 = 1.0 / (1.0 + s / pp.k2);
+  }
+  return pp.alpha + (1.0 - pp.alpha) * g0;
+}
+
+// x pass fused with the magnitude, the diffusivity and the tensor.  Block = 256 consecutive x
+// of one row.  LDS: the three input rows over [x0 - R, x0 + 256 + R), taken at the CLAMPED
+// positions, so a voxel's taps read [i - R, i + R] of the replicated row for any nx (the last
+// block may be narrower than R).  taps = [K0 | K1] of sigma (2 R + 1 each).
+// ih = (1 / hx, 1 / hy, 1 / hz), each applied once to its gradient component.
+// PM_TENSOR: D = the six tensor components (stride cs), gout (optional) = g.
+// PM_GRADIENT: D = gx, gy, gz (stride cs).
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) pm_x_k(const T* __restrict__ a00, const T* __restrict__ a10,
+                                              const T* __restrict__ a01, const T* __restrict__ taps,
+                                              int R, int nx, int ny, int nz, T ihx, T ihy, T ihz,
+                                              int64_t cs, double* __restrict__ D,
+                                              double* __restrict__ gout, PmParams pp) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char ved_smem[];
+  T* L = reinterpret_cast<T*>(ved_smem);
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * 256;
+  const int i = x0 + tid;
+  const int64_t row = ((int64_t)blockIdx.z * ny + blockIdx.y) * nx;
+  const int nw = 256 + 2 * R;
+  for (int e = tid; e < nw; e += 256) {
+    const int64_t q = row + min(max(x0 - R + e, 0), nx - 1);
+    L[e] = a00[q];
+    L[nw + e] = a10[q];
+    L[2 * nw + e] = a01[q];
+  }
+  __syncthreads();
+  if (i >= nx) return;
+  const int W = 2 * R + 1;
+  const T* c = L + tid;
+  T gx = T(0), gy = T(0), gz = T(0);
+#pragma unroll 4
+  for (int q = 0; q < W; ++q) {
+    const T k0 = taps[q], k1 = taps[W + q];
+    gx = fma(k1, c[q], gx);
+    gy = fma(k0, c[nw + q], gy);
+    gz = fma(k0, c[2 * nw + q], gz);
+  }
+  gx = gx * ihx;
+  gy = gy * ihy;
+  gz = gz * ihz;
+  const int64_t p = row + i;
+  if (MODE == PM_GRADIENT) {
+    D[p] = (double)gx;
+    D[cs + p] = (double)gy;
+    D[2 * cs + p] = (double)gz;
+    return;
+  }
+  T s = gx * gx;
+  s = s + gy * gy;
+  s = s + gz * gz;
+  const double g = pm_diffusivity((double)s, pp);
+  D[p] = g;
+  D[cs + p] = 0.0;
+  D[2 * cs + p] = 0.0;
+  D[3 * cs + p] = g;
+  D[4 * cs + p] = 0.0;
+  D[5 * cs + p] = g;
+  if (gout) gout[p] = g;
+}
+
+// ---------------------------------------------------------------------------------------
+// 2D: one fused kernel per tensor generation, modelled on phases A-C of ced2_k.  The halo is
+// the sigma radius alone, so the full 64 x 32 tile stays under half a CU's LDS.
+//
+// Block = 256 threads, a TW x TH output tile at (x0, y0); TW a power of two >= 4, TH a multiple
+// of 4.  LDS holds two regions that the phases use in turn (S1 = the size of the first in
+// elements, from the host):
+//   A  R1  image tile WA x HA = (TW + 2 Rx) x (TH + 2 Ry), clamped, fp64 -> T
+//   B  R2  K0y u, K1y u on the tile's TH rows, all WA staged columns, stored column-major with
+//          the odd pitch TH + 1
+//   C  R1  gx, gy on the TW x TH tile, row pitch TW + 1 (A is dead): K1x / K0x of B's arrays in
+//          registers, four consecutive columns per thread
+//   D       s, the diffusivity, the store; lanes run along x
+// A staged position outside the image holds the value AT THE CLAMPED POSITION.  Every LDS index
+// is tile-relative: B reads the rows [p - y0, p - y0 + 2 Ry] for the clamped row p in
+// [y0, y0 + TH), C the columns [i, i + 2 Rx] for a tile column i < TW, both inside the staged
+// tile for any image size (3 x 3 with halos longer than the axis included); tile positions
+// outside the image are computed from the replicated border and never stored.
+// A thread works on four outputs at a time, so one uniform tap load serves eight fma.  In B
+// the four are the same column of four rows, lanes along the columns.  In C they are
+// consecutive along x and share their input reads (W + 3 reads for 4 outputs instead of 4 W):
+// output j takes input r with the tap r - j, read from a tap row padded with three zeros on
+// either side, so each output still sums its taps t = -R..R in order and the zero taps add
+// nothing; lanes run along the rows.  With B column-major every read of a wave is to
+// consecutive addresses, and the odd pitches keep B's and C's transposing stores off a single
+// bank.  D reads C's rows along x, so a wave's stores are 512 contiguous bytes per component.
+// taps_y: [K0 | K1] of the axis; taps_xp: [0 0 0 K0 0 0 0 | 0 0 0 K1 0 0 0].
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) pm2_k(const double* __restrict__ in, const T* __restrict__ taps_xp,
+                                             const T* __restrict__ taps_y, int Rx, int Ry, int nx,
+                                             int ny, int TW, int TH, int S1, T ihx, T ihy, int64_t cs,
+                                             double* __restrict__ D, double* __restrict__ gout,
+                                             PmParams pp) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char ved_smem[];
+  T* R1 = reinterpret_cast<T*>(ved_smem);
+  T* R2 = R1 + S1;
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+  const int WA = TW + 2 * Rx, HA = TH + 2 * Ry;  // staged image
+  const int PB = TH + 1, PC = TW + 1;            // pitches of B (per column) and C (per row)
+  const int Wx = 2 * Rx + 1, Wy = 2 * Ry + 1;
+  const float iWA = 1.0f / (float)WA;
+  // A: eight loads in flight per thread
+  const int nA = WA * HA;
+  for (int e0 = tid; e0 < nA; e0 += 2048) {
+    double u[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int e = min(e0 + 256 * j, nA - 1);
+      const int r = ced2_div(e, iWA), c = e - r * WA;
+      const int yy = min(max(y0 - Ry + r, 0), ny - 1), xx = min(max(x0 - Rx + c, 0), nx - 1);
+      u[j] = in[(int64_t)yy * nx + xx];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (e0 + 256 * j < nA) R1[e0 + 256 * j] = (T)u[j];
+  }
+  __syncthreads();
+  // B: item = (staged column c, rows 4 g .. 4 g + 3); lanes run along c
+  const int SB = WA * PB;
+  for (int e = tid; e < WA * (TH / 4); e += 256) {
+    const int g = ced2_div(e, iWA), c = e - g * WA;
+    const T* a[4];
+    T b0[4], b1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int p = min(y0 + 4 * g + j, ny - 1);
+      a[j] = R1 + (p - y0) * WA + c;
+      b0[j] = b1[j] = T(0);
+    }
+#pragma unroll 2
+    for (int q = 0; q < Wy; ++q) {
+      const T k0 = taps_y[q], k1 = taps_y[Wy + q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const T v = a[j][q * WA];
+        b0[j] = fma(k0, v, b0[j]);
+        b1[j] = fma(k1, v, b1[j]);
+      }
+    }
+    T* o = R2 + c * PB + 4 * g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[j] = b0[j];
+      o[SB + j] = b1[j];
+    }
+  }
+  __syncthreads();
+  // C: item = (row rb, four consecutive tile columns i0..i0+3); lanes run along rb
+  const int SC = TH * PC;
+  const T* k0p = taps_xp;           // the padded taps: tap t at [3 + R + t]
+  const T* k1p = taps_xp + Wx + 6;
+  const float iTH = 1.0f / (float)TH;
+  for (int e = tid; e < TH * (TW / 4); e += 256) {
+    const int g = ced2_div(e, iTH), rb = e - g * TH, i0 = 4 * g;
+    const T* c = R2 + i0 * PB + rb;
+    T gx[4], gy[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gx[j] = gy[j] = T(0);
+#pragma unroll 2
+    for (int r = 0; r < Wx + 3; ++r) {
+      const T v0 = c[r * PB], v1 = c[SB + r * PB];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        gx[j] = fma(k1p[3 + r - j], v0, gx[j]);
+        gy[j] = fma(k0p[3 + r - j], v1, gy[j]);
+      }
+    }
+    T* o = R1 + rb * PC + i0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[j] = gx[j] * ihx;
+      o[SC + j] = gy[j] * ihy;
+    }
+  }
+  __syncthreads();
+  // D: one pixel per item; lanes run along x
+  const int sh = __ffs(TW) - 1;
+  for (int e = tid; e < TW * TH; e += 256) {
+    const int xi = e & (TW - 1), o = e >> sh;
+    const int i = x0 + xi, y = y0 + o;
+    if (i >= nx || y >= ny) continue;
+    const T gx = R1[o * PC + xi], gy = R1[SC + o * PC + xi];
+    const int64_t p = (int64_t)y * nx + i;
+    if (MODE == PM_GRADIENT) {
+      D[p] = (double)gx;
+      D[cs + p] = (double)gy;
+      continue;
+    }
+    T s = gx * gx;
+    s = s + gy * gy;
+    const double gv = pm_diffusivity((double)s, pp);
+    D[p] = gv;
+    D[cs + p] = 0.0;
+    D[2 * cs + p] = gv;
+    if (gout) gout[p] = gv;
+  }
+}
+
+}  // namespace mad

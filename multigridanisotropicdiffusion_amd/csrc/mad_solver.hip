@@ -3688,3 +3688,4 @@ int mad_comm_init_rccl_solo(mad_ctx* c) {
 // VED pipeline (include/mad_ved.h): the caller of the hot path, same library
 #include "mad_ved.hpp"
 #include "mad_ced.hpp"
+#include "mad_pm.hpp"
