@@ -436,8 +436,20 @@ class PeronaMalikDiffusionImageFilter {
 
   void SetDiffusivity(DiffusivityType g) { desc_.diffusivity = g; }
   void SetNoiseScale(Precision v) { desc_.noise_scale = v; }
-  void SetContrast(Precision v) { desc_.contrast = v; }
+  // an absolute contrast K (leaves quantile mode)
+  void SetContrast(Precision v) {
+    desc_.contrast = v;
+    desc_.contrast_mode = MAD_PM_CONTRAST_ABSOLUTE;
+  }
   void SetConductanceParameter(Precision v) { SetContrast(v); }
+  // K from the q-quantile of the gradient magnitudes, selected on the device in every iteration
+  // (0 < q <= 1; Perona and Malik: 0.9): mad_pm.h, "Contrast from a quantile"
+  void SetContrastQuantile(Precision q) {
+    desc_.contrast = q;
+    desc_.contrast_mode = MAD_PM_CONTRAST_QUANTILE;
+  }
+  // K of the last tensor generation of the last Update (0 before it)
+  Precision GetContrastUsed() const { return stats_.contrast_used; }
   void SetExponent(Precision v) { desc_.exponent = v; }
   void SetAlpha(Precision v) { desc_.alpha = v; }
   void SetIterations(unsigned int n) { desc_.iterations = n; }

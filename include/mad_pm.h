@@ -29,6 +29,24 @@
  *      diffusion_iterations = 1, iterations = n.
  * See DESIGN.md "Nonlinear isotropic diffusion (Perona-Malik)" and tests/pm_numpy.py.
  *
+ * Contrast from a quantile (contrast_mode = MAD_PM_CONTRAST_QUANTILE).  K is in units of the
+ * image's own gradient; Perona and Malik set it from the data, once per iteration, as the value
+ * below which 90 % of the gradient magnitudes lie.  In this mode `contrast` holds that share q,
+ * 0 < q <= 1, and every tensor generation finds its K on the device:
+ *   rank   with s(p) of step 2 over all N voxels, k = min(N - 1, max(0, (int64)ceil(q (double)N) - 1))
+ *          (product and ceil in fp64 on the host), s_q = the k-th smallest s(p), 0-based:
+ *          numpy's np.quantile(s, q, method="inverted_cdf").  The selection is exact.
+ *   map    step 3 with K^2 := s_q, used as it is (never via sqrt and squaring); the K reported
+ *          (mad_pm_stats.contrast_used) is sqrt(s_q).  K^2 stays in device memory between the
+ *          selection and the map: a tensor generation has no host synchronisation.
+ *   s_q = 0 (a constant image, or more than the share q of the voxels flat): the limit K -> 0+ of
+ *          all three diffusivities, g0 = 1 where s = 0 and g0 = 0 elsewhere; K is reported as 0,
+ *          a valid result.
+ *   In mad_pm_run / mad_pm_run_device every outer iteration selects anew from its iterate.
+ * The mode needs N < 2^32 (mad_pm_create refuses more).  Its entry points for inspection,
+ * mad_pm_contrast and mad_pm_select, are declared in mad_pm_quantile.h.  See DESIGN.md
+ * "Contrast from a quantile" and tests/pm_quantile_numpy.py.
+ *
  * Limit on sigma.  Every kernel keeps its tile and the taps' halo in 128 KiB of LDS and shrinks
  * the tile for long taps; taps that do not fit the smallest tile make mad_pm_run,
  * mad_pm_tensor and mad_pm_gradient return MAD_ERR_UNSUPPORTED ("Gaussian taps too long for
@@ -65,13 +83,23 @@ typedef enum mad_pm_diffusivity {
   MAD_PM_RATIONAL = 2              /* 1 / (1 + s / K^2): Perona and Malik's second function */
 } mad_pm_diffusivity;
 
+typedef enum mad_pm_contrast_mode {
+  MAD_PM_CONTRAST_ABSOLUTE = 0,    /* contrast is K itself */
+  MAD_PM_CONTRAST_QUANTILE = 1     /* contrast is q, 0 < q <= 1: K^2 = the q-quantile of s, per tensor
+                                      generation ("Contrast from a quantile" above) */
+} mad_pm_contrast_mode;
+
+/* mad_pm_desc.options.  Test only: in MAD_PM_CONTRAST_ABSOLUTE, `contrast` holds K^2 itself, fed to
+ * the map unsquared, so a test can give the fused kernel the very bits a selection returned. */
+#define MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED 0x80000000u
+
 typedef struct mad_pm_desc {
   uint32_t abi_version;            /* MAD_ABI_VERSION */
   int64_t size[3];                 /* x, y, z (dim 2: z = 1) */
   double spacing[3];               /* image spacing, x first (dim 2: spacing[2] is ignored) */
   int32_t diffusivity;             /* mad_pm_diffusivity, MAD_PM_WEICKERT */
   double noise_scale;              /* sigma, physical units, 0.5 */
-  double contrast;                 /* K, 1.0 */
+  double contrast;                 /* K, 1.0 (MAD_PM_CONTRAST_QUANTILE: the share q) */
   double exponent;                 /* m, 2.0 (MAD_PM_WEICKERT only) */
   double alpha;                    /* 0 < alpha < 1, 0.01 */
   uint32_t iterations;             /* 1  (outer iterations: tensor generation + diffusion) */
@@ -88,9 +116,11 @@ typedef struct mad_pm_desc {
                                       in every mode. */
   int32_t device;                  /* HIP device, -1 = current */
   int32_t verbose;                 /* 0 */
-  uint32_t options;                /* reserved, 0 */
+  uint32_t options;                /* 0 (MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED: tests only) */
   int32_t dim;                     /* 3 (default; 0 is read as 3) or 2; anything else is invalid */
-  int32_t reserved[4];
+  int32_t contrast_mode;           /* mad_pm_contrast_mode, MAD_PM_CONTRAST_ABSOLUTE (the word was
+                                      reserved[0], which every earlier caller left 0) */
+  int32_t reserved[3];
 } mad_pm_desc;
 
 typedef struct mad_pm_stats {
@@ -100,11 +130,24 @@ typedef struct mad_pm_stats {
   double tensor_ms;                /* device time of the tensor generations, all iterations */
   double diffusion_ms;             /* MAD setup + solve, all iterations */
   double pass_ms[3];               /* device time per pass (z, y, x + map), summed over the
-                                      iterations; dim 2: [0] is the fused kernel, [1..2] are 0 */
+                                      iterations; dim 2: [0] is the fused kernel, [1..2] are 0.
+                                      Quantile mode: the selection and the map kernel count with
+                                      the last pass ([2], dim 2: [0]) */
   int32_t stalled;                 /* any step ended by the fp32 stall guard */
   int32_t tile[2];                 /* dim 2: the fused kernel's output tile (x, y); 0 in 3D */
-  int32_t reserved[5];
+  double contrast_used;            /* K of this run's last tensor generation: sqrt(s_q) in quantile mode (0
+                                      when s_q = 0, and 0 for a run with iterations = 0, which has no
+                                      generation), else the descriptor's contrast */
+  int32_t reserved[2];
 } mad_pm_stats;
+
+/* the layout did not move: contrast_mode took reserved[0]; contrast_used, behind 4 bytes of
+ * padding, took the stats' reserved[0..2] */
+#if defined(__cplusplus)
+static_assert(sizeof(mad_pm_desc) == 176 && sizeof(mad_pm_stats) == 88, "mad_pm.h layout");
+#else
+_Static_assert(sizeof(mad_pm_desc) == 176 && sizeof(mad_pm_stats) == 88, "mad_pm.h layout");
+#endif
 
 typedef struct mad_pm_ctx mad_pm_ctx;
 

@@ -75,6 +75,13 @@ PM_EXPORTS = (
     "mad_pm_run", "mad_pm_run_device", "mad_pm_tensor", "mad_pm_gradient",
 )
 
+# include/mad_pm_quantile.h (the quantile mode's inspection entry points, a header of their own)
+PM_QUANTILE_EXPORTS = ("mad_pm_contrast", "mad_pm_select")
+
+# mad_pm_contrast_mode and the test-only option bit (include/mad_pm.h)
+PM_CONTRAST_ABSOLUTE, PM_CONTRAST_QUANTILE = 0, 1
+PM_OPT_TEST_CONTRAST_IS_SQUARED = 0x80000000
+
 VED_MAX_SCALES = 16
 
 
@@ -223,8 +230,16 @@ class CedStats(ctypes.Structure):
         return d
 
 
+class _PmDescTail(ctypes.Union):
+    """The last four words of mad_pm_desc: contrast_mode took the first reserved word.  `reserved`
+    stays the four-word view bindings of the earlier layout read (word 0 is contrast_mode, 0 =
+    absolute in every descriptor written before the mode existed)."""
+    _fields_ = [("contrast_mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+
+
 class PmDesc(ctypes.Structure):
     """mad_pm_desc (include/mad_pm.h)."""
+    _anonymous_ = ("_tail",)
     _fields_ = [
         ("abi_version", ctypes.c_uint32),
         ("size", ctypes.c_int64 * 3),
@@ -246,7 +261,7 @@ class PmDesc(ctypes.Structure):
         ("verbose", ctypes.c_int32),
         ("options", ctypes.c_uint32),
         ("dim", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 4),
+        ("_tail", _PmDescTail),
     ]
 
 
@@ -260,11 +275,14 @@ class PmStats(ctypes.Structure):
         ("pass_ms", ctypes.c_double * 3),
         ("stalled", ctypes.c_int32),
         ("tile", ctypes.c_int32 * 2),
-        ("reserved", ctypes.c_int32 * 5),
+        ("contrast_used", ctypes.c_double),
+        ("reserved", ctypes.c_int32 * 2),
     ]
 
     def as_dict(self):
-        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("reserved", "pass_ms", "tile")}
+        """The fields an absolute-mode run reports (pm.py adds contrast_used in quantile mode)."""
+        d = {f: getattr(self, f) for f, _ in self._fields_
+             if f not in ("reserved", "pass_ms", "tile", "contrast_used")}
         d["pass_ms"] = list(self.pass_ms)
         d["tile"] = tuple(self.tile)
         return d
@@ -373,6 +391,8 @@ def load():
         "mad_pm_run_device": ([vp, vp, i32, vp, i32, ctypes.POINTER(PmStats)], i32),
         "mad_pm_tensor": ([vp, vp, i32, dp, dp], i32),
         "mad_pm_gradient": ([vp, vp, i32, dp], i32),
+        "mad_pm_contrast": ([vp, vp, i32, dbl, dp], i32),
+        "mad_pm_select": ([vp, dp, i64, i64, dp], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmad_hip.so")
 SOURCES = ["mad_solver.hip"]
 DEPS = ["../../include/mad.h", "../../include/mad_ved.h", "../../include/mad_ced.h",
-        "../../include/mad_pm.h"]
+        "../../include/mad_pm.h", "../../include/mad_pm_quantile.h"]
 
 
 def deps():

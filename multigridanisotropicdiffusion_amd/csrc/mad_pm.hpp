@@ -4,7 +4,9 @@
 // device tensor to the MAD solver in place (tensor_at0) and runs the diffusion steps through
 // run_impl, no host round trips between tensor generation and solve.
 #include "../../include/mad_pm.h"
+#include "../../include/mad_pm_quantile.h"
 #include "mad_pm_kernels.hpp"
+#include "mad_select.hpp"
 
 struct mad_pm_ctx {
   mad_pm_desc d{};
@@ -23,16 +25,26 @@ struct mad_pm_ctx {
   double* gdev = nullptr;  // the diffusivity (mad_pm_tensor only)
   void* stage = nullptr;   // host <-> device staging
   size_t stage_bytes = 0;
+  // quantile mode, mad_pm_contrast and mad_pm_select only; all allocated on first use
+  bool quantile = false;   // contrast_mode == MAD_PM_CONTRAST_QUANTILE
+  void* sq = nullptr;      // s in the storage precision
+  SelScratch sel;          // the selection's histograms, state and candidate list
+  // pinned, two words, each copied behind its selection on the stream: [kK2Generation] K^2 of the
+  // last tensor generation, [kK2Inspection] the result of mad_pm_contrast / mad_pm_select
+  double* k2_host = nullptr;
   ~mad_pm_ctx() {
     if (mad) (void)hipSetDevice(mad->device);
     if (mad && mad->stream) (void)hipStreamSynchronize(mad->stream);
-    for (void* p : {(void*)img, (void*)img2, vol, taps, (void*)gdev, stage})
+    for (void* p : {(void*)img, (void*)img2, vol, taps, (void*)gdev, stage, sq, sel.work, sel.list})
       if (p) (void)hipFree(p);
+    if (k2_host) (void)hipHostFree(k2_host);
     if (mad) mad_destroy(mad);
   }
 };
 
 namespace {
+
+enum { kK2Generation = 0, kK2Inspection = 1 };
 
 // ced_guarded's status mapping, the message kept on this context
 template <typename F>
@@ -72,7 +84,8 @@ void pm_lds_attr() {
   static bool done = false;
   if (done) return;
   for (const void* k : {(const void*)pm_x_k<T, PM_TENSOR>, (const void*)pm_x_k<T, PM_GRADIENT>,
-                        (const void*)pm2_k<T, PM_TENSOR>, (const void*)pm2_k<T, PM_GRADIENT>})
+                        (const void*)pm_x_k<T, PM_SQNORM>, (const void*)pm2_k<T, PM_TENSOR>,
+                        (const void*)pm2_k<T, PM_GRADIENT>, (const void*)pm2_k<T, PM_SQNORM>})
     HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVedLds));
   done = true;
 }
@@ -99,11 +112,70 @@ void pm_upload_taps(mad_pm_ctx* v) {
   HIP_CHECK(hipMemcpy(v->taps, kt.data(), sizeof(T) * kt.size(), hipMemcpyHostToDevice));
 }
 
+// the map's parameters in absolute mode (quantile mode: k2 comes from the selection)
+PmParams pm_params(const mad_pm_ctx* v) {
+  const bool squared = v->d.options & MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED;
+  return {v->d.diffusivity, squared ? v->d.contrast : v->d.contrast * v->d.contrast, v->d.exponent, v->d.alpha};
+}
+
+// the rank of the quantile q among n values (include/mad_pm.h): numpy's inverted_cdf
+int64_t pm_rank(double q, int64_t n) {
+  const int64_t k = (int64_t)std::ceil(q * (double)n) - 1;
+  return std::min<int64_t>(n - 1, std::max<int64_t>(0, k));
+}
+
+// the selection's scratch for n keys of key_bytes, on first use (the list grows on demand)
+void pm_select_scratch(mad_pm_ctx* v, int64_t n, size_t key_bytes) {
+  REQUIRE(n < ((int64_t)1 << 32), MAD_ERR_UNSUPPORTED, "the selection counts in 32 bits: fewer than 2^32 values");
+  if (!v->sel.work) HIP_CHECK(hipMalloc(&v->sel.work, SelScratch::work_bytes));
+  if (!v->k2_host) HIP_CHECK(hipHostMalloc((void**)&v->k2_host, 2 * sizeof(double), hipHostMallocDefault));
+  const size_t need = n >= kSelListMin ? key_bytes * (size_t)n : 0;
+  if (need > v->sel.list_bytes) {
+    if (v->sel.list) HIP_CHECK(hipFree(v->sel.list));
+    v->sel.list = nullptr;
+    v->sel.list_bytes = 0;
+    HIP_CHECK(big_alloc(&v->sel.list, need));
+    v->sel.list_bytes = need;
+  }
+}
+
+// Quantile mode behind a PM_SQNORM pass: selects s_q among v->sq (rank of q), leaves K^2 in device
+// memory and sends a copy to v->k2_host behind it (with D, a tensor generation: the generation's
+// word, else the inspection's); with D, maps s -> g -> D.  No host
+// synchronisation: the phases follow each other on the stream.
+template <typename T>
+void pm_select_and_map(mad_pm_ctx* v, double q, double* D, int64_t cs, double* gout) {
+  using Key = typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type;
+  hipStream_t st = v->mad->stream;
+  HIP_CHECK(select_launch<Key>(v->sel, (const Key*)v->sq, v->N, pm_rank(q, v->N), st));
+  HIP_CHECK(hipMemcpyAsync(v->k2_host + (D ? kK2Generation : kK2Inspection), v->sel.value(), sizeof(double),
+                           hipMemcpyDeviceToHost, st));
+  if (!D) return;
+  const unsigned blocks = (unsigned)std::min<int64_t>((v->N + 255) / 256, 8192);
+  const PmParams pp = pm_params(v);
+  if (v->dim == 2)
+    hipLaunchKernelGGL((pm_map_k<T, 3>), dim3(blocks), dim3(256), 0, st, (const T*)v->sq, v->sel.value(), v->N, cs,
+                       D, gout, pp);
+  else
+    hipLaunchKernelGGL((pm_map_k<T, 6>), dim3(blocks), dim3(256), 0, st, (const T*)v->sq, v->sel.value(), v->N, cs,
+                       D, gout, pp);
+}
+
+// s of v->img in the storage precision, on first use
+template <typename T>
+T* pm_sq(mad_pm_ctx* v) {
+  pm_select_scratch(v, v->N, sizeof(T));
+  if (!v->sq) HIP_CHECK(big_alloc(&v->sq, sizeof(T) * v->N));
+  return (T*)v->sq;
+}
+
 // One 3D tensor generation from v->img: ced_z_k, ced_y_k, pm_x_k.  mode PM_TENSOR: D = the
 // tensor (component stride cs), gout optional; PM_GRADIENT: D = (gx, gy, gz).  ev: four events
-// around the passes (may be null).
+// around the passes (may be null).  q > 0 (quantile mode): the x pass stores s alone, then the
+// selection of the quantile q and, in PM_TENSOR, the map kernel follow (PM_SQNORM: K^2 only, D
+// unused); all three count with the last pass.
 template <typename T>
-void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, Event* ev) {
+void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, Event* ev, double q) {
   hipStream_t st = v->mad->stream;
   const int nx = (int)v->n[0], ny = (int)v->n[1], nz = (int)v->n[2];
   const int64_t N = v->N;
@@ -118,6 +190,7 @@ void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, E
   REQUIRE(l1 <= kVedLds && l2 <= kVedLds && l3 <= kVedLds, MAD_ERR_UNSUPPORTED,
           "Gaussian taps too long for the LDS tiles (scale / spacing too large)");
   if (!v->vol) HIP_CHECK(big_alloc((void**)&v->vol, sizeof(T) * 5 * N));
+  T* sq = q > 0.0 ? pm_sq<T>(v) : nullptr;
   T* f = (T*)v->vol;
   T *z0 = f, *z1 = f + N, *a00 = f + 2 * N, *a10 = f + 3 * N, *a01 = f + 4 * N;
   ced_lds_attr<T>();
@@ -125,7 +198,7 @@ void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, E
   const T* tp = (const T*)v->taps;
   const double* h = v->d.spacing;
   const T ihx = (T)(1.0 / h[0]), ihy = (T)(1.0 / h[1]), ihz = (T)(1.0 / h[2]);
-  const PmParams pp{v->d.diffusivity, v->d.contrast * v->d.contrast, v->d.exponent, v->d.alpha};
+  const PmParams pp = pm_params(v);
   if (ev) HIP_CHECK(hipEventRecord(ev[0], st));
   hipLaunchKernelGGL((ced_z_k<T>), dim3((nx + 63) / 64, (ny + 3) / 4, (nz + ZT - 1) / ZT), dim3(256), l1, st,
                      v->img, z0, z1, tp + v->tap_off[2], R[2], nx, ny, nz, ZT);
@@ -134,10 +207,14 @@ void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, E
                      a00, a10, a01, tp + v->tap_off[1], R[1], nx, ny, nz, YT);
   if (ev) HIP_CHECK(hipEventRecord(ev[2], st));
   const dim3 g3((nx + 255) / 256, ny, nz);
-  if (mode == PM_GRADIENT)
+  if (mode == PM_GRADIENT) {
     hipLaunchKernelGGL((pm_x_k<T, PM_GRADIENT>), g3, dim3(256), l3, st, a00, a10, a01, tp + v->tap_off[0],
                        R[0], nx, ny, nz, ihx, ihy, ihz, cs, D, nullptr, pp);
-  else
+  } else if (sq) {
+    hipLaunchKernelGGL((pm_x_k<T, PM_SQNORM>), g3, dim3(256), l3, st, a00, a10, a01, tp + v->tap_off[0], R[0],
+                       nx, ny, nz, ihx, ihy, ihz, cs, (double*)sq, nullptr, pp);
+    pm_select_and_map<T>(v, q, mode == PM_TENSOR ? D : nullptr, cs, gout);
+  } else
     hipLaunchKernelGGL((pm_x_k<T, PM_TENSOR>), g3, dim3(256), l3, st, a00, a10, a01, tp + v->tap_off[0], R[0],
                        nx, ny, nz, ihx, ihy, ihz, cs, D, gout, pp);
   if (ev) HIP_CHECK(hipEventRecord(ev[3], st));
@@ -155,9 +232,9 @@ Pm2Lds pm2_lds(int TW, int TH, const int* R) {
 }
 
 // 2D: one tensor generation from v->img by the fused kernel.  ev: events around it (ev[0],
-// ev[1]; ev[2..3] follow at once so the 3D bookkeeping holds).
+// ev[1]; ev[2..3] follow at once so the 3D bookkeeping holds).  q as in pm_generate.
 template <typename T>
-void pm2_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, Event* ev) {
+void pm2_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, Event* ev, double q) {
   hipStream_t st = v->mad->stream;
   const int nx = (int)v->n[0], ny = (int)v->n[1];
   const int* R = v->R;
@@ -179,20 +256,25 @@ void pm2_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, 
           "Gaussian taps too long for the LDS tiles (scale / spacing too large)");
   v->tile[0] = TW;
   v->tile[1] = TH;
+  T* sq = q > 0.0 ? pm_sq<T>(v) : nullptr;
   pm_lds_attr<T>();
   const T* tp = (const T*)v->taps;
   const T* txp = tp + v->tap_off[0] + 2 * (2 * R[0] + 1);  // the padded x taps
   const T* ty = tp + v->tap_off[1];
   const double* h = v->d.spacing;
   const T ihx = (T)(1.0 / h[0]), ihy = (T)(1.0 / h[1]);
-  const PmParams pp{v->d.diffusivity, v->d.contrast * v->d.contrast, v->d.exponent, v->d.alpha};
+  const PmParams pp = pm_params(v);
   const dim3 grid((nx + TW - 1) / TW, (ny + TH - 1) / TH);
   const int s1 = pm2_lds(TW, TH, R).s1;
   if (ev) HIP_CHECK(hipEventRecord(ev[0], st));
-  if (mode == PM_GRADIENT)
+  if (mode == PM_GRADIENT) {
     hipLaunchKernelGGL((pm2_k<T, PM_GRADIENT>), grid, dim3(256), lds, st, v->img, txp, ty, R[0], R[1], nx, ny,
                        TW, TH, s1, ihx, ihy, cs, D, nullptr, pp);
-  else
+  } else if (sq) {
+    hipLaunchKernelGGL((pm2_k<T, PM_SQNORM>), grid, dim3(256), lds, st, v->img, txp, ty, R[0], R[1], nx, ny, TW,
+                       TH, s1, ihx, ihy, cs, (double*)sq, nullptr, pp);
+    pm_select_and_map<T>(v, q, mode == PM_TENSOR ? D : nullptr, cs, gout);
+  } else
     hipLaunchKernelGGL((pm2_k<T, PM_TENSOR>), grid, dim3(256), lds, st, v->img, txp, ty, R[0], R[1], nx, ny, TW,
                        TH, s1, ihx, ihy, cs, D, gout, pp);
   if (ev)
@@ -200,19 +282,27 @@ void pm2_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, 
   HIP_CHECK(hipGetLastError());
 }
 
-void pm_generate_any(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, Event* ev) {
+// q: the quantile of quantile mode (PM_TENSOR in a quantile context, PM_SQNORM anywhere), else 0
+void pm_generate_any(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, Event* ev, double q = 0.0) {
   const bool f64 = v->d.precision == MAD_FP64;
-  if (v->dim == 2 && f64) pm2_generate<double>(v, mode, D, cs, gout, ev);
-  else if (v->dim == 2) pm2_generate<float>(v, mode, D, cs, gout, ev);
-  else if (f64) pm_generate<double>(v, mode, D, cs, gout, ev);
-  else pm_generate<float>(v, mode, D, cs, gout, ev);
+  if (v->dim == 2 && f64) pm2_generate<double>(v, mode, D, cs, gout, ev, q);
+  else if (v->dim == 2) pm2_generate<float>(v, mode, D, cs, gout, ev, q);
+  else if (f64) pm_generate<double>(v, mode, D, cs, gout, ev, q);
+  else pm_generate<float>(v, mode, D, cs, gout, ev, q);
+}
+
+// K of a run's last tensor generation (generated: the run had one); quantile mode: valid once the
+// stream has been synchronised, and 0 for a run without a generation (iterations = 0)
+double pm_contrast_used(const mad_pm_ctx* v, bool generated) {
+  if (v->quantile) return generated && v->k2_host ? std::sqrt(v->k2_host[kK2Generation]) : 0.0;
+  return v->d.options & MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED ? std::sqrt(v->d.contrast) : v->d.contrast;
 }
 
 // the tensor of v->img into the solver's tensor storage; the solver's setup is redone
 void pm_tensor_to_solver(mad_pm_ctx* v, double* gout, Event* ev) {
   mad_ctx* c = v->mad;
   tensor_alloc(c);
-  pm_generate_any(v, PM_TENSOR, tensor_at0(c), c->tensor_cs, gout, ev);
+  pm_generate_any(v, PM_TENSOR, tensor_at0(c), c->tensor_cs, gout, ev, v->quantile ? v->d.contrast : 0.0);
   c->tensor_set = true;
   c->setup_done = false;
 }
@@ -260,6 +350,7 @@ void pm_run_impl(mad_pm_ctx* v, const void* in, int in_dt, void* out, int out_dt
     st->stalled = stalled;
     st->tile[0] = v->tile[0];
     st->tile[1] = v->tile[1];
+    st->contrast_used = pm_contrast_used(v, v->d.iterations > 0);
   }
 }
 
@@ -313,17 +404,37 @@ int mad_pm_create(const mad_pm_desc* d, mad_pm_ctx** out) {
                 d->diffusivity == MAD_PM_RATIONAL,
             MAD_ERR_INVALID, "unknown diffusivity (MAD_PM_WEICKERT, MAD_PM_EXPONENTIAL or MAD_PM_RATIONAL)");
     REQUIRE(d->noise_scale > 0.0, MAD_ERR_INVALID, "noise_scale must be positive");
+    REQUIRE(d->contrast_mode == MAD_PM_CONTRAST_ABSOLUTE || d->contrast_mode == MAD_PM_CONTRAST_QUANTILE,
+            MAD_ERR_INVALID, "unknown contrast_mode (MAD_PM_CONTRAST_ABSOLUTE or MAD_PM_CONTRAST_QUANTILE)");
+    const bool quantile = d->contrast_mode == MAD_PM_CONTRAST_QUANTILE;
+    if (quantile)
+      REQUIRE(d->contrast > 0.0 && d->contrast <= 1.0, MAD_ERR_INVALID,
+              "MAD_PM_CONTRAST_QUANTILE: contrast holds the quantile q, 0 < q <= 1");
     REQUIRE(d->contrast > 0.0, MAD_ERR_INVALID, "contrast must be positive");
     REQUIRE(d->exponent > 0.0, MAD_ERR_INVALID, "exponent must be positive");
     REQUIRE(d->alpha > 0.0 && d->alpha < 1.0, MAD_ERR_INVALID, "alpha must lie in (0, 1)");
-    REQUIRE(d->options == 0, MAD_ERR_INVALID, "unknown option bits");
+    REQUIRE((d->options & ~MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED) == 0, MAD_ERR_INVALID, "unknown option bits");
+    REQUIRE(!(d->options & MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED) || !quantile, MAD_ERR_INVALID,
+            "MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED goes with MAD_PM_CONTRAST_ABSOLUTE");
     const int dim = d->dim == 0 ? 3 : d->dim;
     REQUIRE(dim == 2 || dim == 3, MAD_ERR_INVALID, "dim must be 2 or 3 (0 is read as 3)");
     REQUIRE(dim == 3 || d->size[2] == 1, MAD_ERR_INVALID, "dim 2 needs size[2] == 1");
     for (int q = 0; q < dim; ++q)
       REQUIRE(d->spacing[q] > 0.0, MAD_ERR_INVALID, "spacing must be positive");
+    if (quantile) {
+      // the selection counts in 32 bits
+      bool fits = true;
+      int64_t total = 1;
+      for (int q = 0; q < 3 && fits; ++q) {
+        const int64_t nq = d->size[q];
+        fits = nq >= 1 && nq <= (int64_t)UINT32_MAX / total;
+        if (fits) total *= nq;
+      }
+      REQUIRE(fits, MAD_ERR_INVALID, "MAD_PM_CONTRAST_QUANTILE needs 1 <= N < 2^32 voxels");
+    }
     v->d = *d;
     v->dim = dim;
+    v->quantile = quantile;
     mad_desc md;
     mad_desc_init(&md);
     md.dim = dim;
@@ -410,6 +521,34 @@ int mad_pm_gradient(mad_pm_ctx* v, const void* image, int32_t dtype, double* gra
     HIP_CHECK(hipMemcpyAsync(grad_soa, G, sizeof(double) * v->dim * v->N, hipMemcpyDeviceToHost,
                              v->mad->stream));
     HIP_CHECK(hipStreamSynchronize(v->mad->stream));
+  });
+}
+
+int mad_pm_contrast(mad_pm_ctx* v, const void* image, int32_t dtype, double q, double* contrast) {
+  if (!v || !image || !contrast) return MAD_ERR_INVALID;
+  return pm_guarded(v, [&] {
+    REQUIRE(q > 0.0 && q <= 1.0, MAD_ERR_INVALID, "the quantile q must lie in (0, 1]");
+    HIP_CHECK(hipSetDevice(v->mad->device));
+    pm_load_image(v, image, dtype, false);
+    pm_generate_any(v, PM_SQNORM, nullptr, v->N, nullptr, nullptr, q);
+    HIP_CHECK(hipStreamSynchronize(v->mad->stream));
+    *contrast = std::sqrt(v->k2_host[kK2Inspection]);
+  });
+}
+
+int mad_pm_select(mad_pm_ctx* v, const double* values, int64_t n, int64_t k, double* out) {
+  if (!v || !values || !out) return MAD_ERR_INVALID;
+  return pm_guarded(v, [&] {
+    REQUIRE(n >= 1 && k >= 0 && k < n, MAD_ERR_INVALID, "mad_pm_select needs n >= 1 and 0 <= k < n");
+    HIP_CHECK(hipSetDevice(v->mad->device));
+    pm_select_scratch(v, n, sizeof(uint64_t));
+    hipStream_t st = v->mad->stream;
+    void* keys = pm_stage(v, sizeof(double) * (size_t)n);
+    HIP_CHECK(hipMemcpyAsync(keys, values, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_CHECK(select_launch<uint64_t>(v->sel, (const uint64_t*)keys, n, k, st));
+    HIP_CHECK(hipMemcpyAsync(v->k2_host + kK2Inspection, v->sel.value(), sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    *out = v->k2_host[kK2Inspection];
   });
 }
 

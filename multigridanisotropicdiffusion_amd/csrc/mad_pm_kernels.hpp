@@ -11,6 +11,9 @@
 //                 the six tensor components
 // Algorithmic traffic in fp32: 16 + 20 + 60 = 96 B per voxel (EED / CED: 192).
 // 2D images take one fused kernel, pm2_k at the end of this file: 8 + 24 = 32 B per pixel.
+// Quantile mode (contrast from a gradient quantile) splits the last step: pm_x_k / pm2_k in the
+// mode PM_SQNORM store s alone (T per voxel), mad_select.hpp selects s_q, and pm_map_k maps
+// s -> g -> D with K^2 = s_q read from device memory.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,7 +31,7 @@ struct PmParams {
   double alpha;
 };
 
-enum { PM_TENSOR = 0, PM_GRADIENT = 1 };
+enum { PM_TENSOR = 0, PM_GRADIENT = 1, PM_SQNORM = 2 };
 
 // g(s) = alpha + (1 - alpha) g0(s), fp64; the default exponent 2 (and 1) skips pow, as ced2_stop
 __device__ inline double pm_diffusivity(double s, const PmParams& pp) {
@@ -49,6 +52,40 @@ __device__ inline double pm_diffusivity(double s, const PmParams& pp) {
   return pp.alpha + (1.0 - pp.alpha) * g0;
 }
 
+// Quantile mode's map: K^2 = s_q comes from the selection.  s_q = 0 (a constant image, or more
+// than the share q of the voxels flat) takes the limit K -> 0+ of all three functions, g0 = 1
+// where s = 0 and 0 elsewhere, instead of their 0 / 0; otherwise the function above.
+__device__ inline double pm_diffusivity_selected(double s, const PmParams& pp) {
+#pragma clang fp contract(off)
+  if (pp.k2 == 0.0) return pp.alpha + (1.0 - pp.alpha) * (s == 0.0 ? 1.0 : 0.0);
+  return pm_diffusivity(s, pp);
+}
+
+// Pointwise map of quantile mode, s -> g -> D: s (storage precision, from a PM_SQNORM pass) and
+// K^2 from device memory (the selection's result; pp.k2 is ignored) to the SoA tensor with
+// component stride cs (ncomp 6: [xx,xy,xz,yy,yz,zz], 3: [xx,xy,yy]) and, optionally, g.
+// T in, 8 ncomp out: 52 B per voxel in 3D fp32, 28 B per pixel in 2D fp32.
+template <typename T, int NCOMP>
+__global__ void __launch_bounds__(256) pm_map_k(const T* __restrict__ s, const double* __restrict__ k2,
+                                                int64_t n, int64_t cs, double* __restrict__ D,
+                                                double* __restrict__ gout, PmParams pp) {
+  pp.k2 = *k2;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+    const double g = pm_diffusivity_selected((double)s[p], pp);
+    D[p] = g;
+    D[cs + p] = 0.0;
+    if (NCOMP == 6) {
+      D[2 * cs + p] = 0.0;
+      D[3 * cs + p] = g;
+      D[4 * cs + p] = 0.0;
+      D[5 * cs + p] = g;
+    } else {
+      D[2 * cs + p] = g;
+    }
+    if (gout) gout[p] = g;
+  }
+}
+
 // x pass fused with the magnitude, the diffusivity and the tensor.  Block = 256 consecutive x
 // of one row.  LDS: the three input rows over [x0 - R, x0 + 256 + R), taken at the CLAMPED
 // positions, so a voxel's taps read [i - R, i + R] of the replicated row for any nx (the last
@@ -56,6 +93,7 @@ __device__ inline double pm_diffusivity(double s, const PmParams& pp) {
 // ih = (1 / hx, 1 / hy, 1 / hz), each applied once to its gradient component.
 // PM_TENSOR: D = the six tensor components (stride cs), gout (optional) = g.
 // PM_GRADIENT: D = gx, gy, gz (stride cs).
+// PM_SQNORM: D is read as T*: s in the storage precision and nothing else (quantile mode).
 template <typename T, int MODE>
 __global__ void __launch_bounds__(256) pm_x_k(const T* __restrict__ a00, const T* __restrict__ a10,
                                               const T* __restrict__ a01, const T* __restrict__ taps,
@@ -101,6 +139,10 @@ __global__ void __launch_bounds__(256) pm_x_k(const T* __restrict__ a00, const T
   T s = gx * gx;
   s = s + gy * gy;
   s = s + gz * gz;
+  if (MODE == PM_SQNORM) {
+    reinterpret_cast<T*>(D)[p] = s;
+    return;
+  }
   const double g = pm_diffusivity((double)s, pp);
   D[p] = g;
   D[cs + p] = 0.0;
@@ -243,6 +285,10 @@ __global__ void __launch_bounds__(256) pm2_k(const double* __restrict__ in, cons
     }
     T s = gx * gx;
     s = s + gy * gy;
+    if (MODE == PM_SQNORM) {
+      reinterpret_cast<T*>(D)[p] = s;
+      continue;
+    }
     const double gv = pm_diffusivity((double)s, pp);
     D[p] = gv;
     D[cs + p] = 0.0;

@@ -36,14 +36,22 @@ def _diffusivity(v):
 
 class _Context:
     """One mad_pm_ctx of dimension DIM (the body PM and PM2D share).  shape: numpy, x last;
-    spacing x first.  diffusivity: "weickert" / "exponential" / "rational" (or C.PM_*)."""
+    spacing x first.  diffusivity: "weickert" / "exponential" / "rational" (or C.PM_*).
+    contrast_quantile=q (0 < q <= 1) overrides contrast: every tensor generation takes K^2 as the
+    q-quantile of the squared gradient magnitudes, selected on the device (include/mad_pm.h,
+    "Contrast from a quantile"); run then reports the last K as stats["contrast_used"].  The
+    attribute contrast_used holds the K of the last run in both modes: run sets it, it is None
+    before the first run, and 0.0 after a quantile-mode run with iterations = 0 (no generation).
+    _contrast_squared is for tests only: an absolute K^2 fed to the map unsquared
+    (MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED)."""
 
     DIM = None
 
     def __init__(self, shape, spacing=None, *, diffusivity="weickert", noise_scale=0.5, contrast=1.0,
                  exponent=2.0, alpha=0.01, iterations=1, diffusion_iterations=5, cycle=C.VCYCLE,
                  time_step=0.1, tolerance=1e-6, diffusion_iterations_per_grid=2, verbose=False,
-                 smoother=C.GAUSS_SEIDEL, precision=C.PRECISION_AUTO, device=-1):
+                 smoother=C.GAUSS_SEIDEL, precision=C.PRECISION_AUTO, device=-1, contrast_quantile=None,
+                 _contrast_squared=None):
         dim = self.DIM
         if len(shape) != dim:
             raise ValueError(f"{type(self).__name__} takes a {dim}D shape (PM: volumes, PM2D: images)")
@@ -65,6 +73,16 @@ class _Context:
         d.diffusion_iterations_per_grid = int(diffusion_iterations_per_grid)
         d.verbose = int(bool(verbose))
         d.smoother, d.precision, d.device = int(smoother), int(precision), int(device)
+        if contrast_quantile is not None and _contrast_squared is not None:
+            raise ValueError("contrast_quantile and _contrast_squared exclude each other")
+        if contrast_quantile is not None:
+            d.contrast_mode, d.contrast = C.PM_CONTRAST_QUANTILE, float(contrast_quantile)
+        elif _contrast_squared is not None:
+            d.options, d.contrast = C.PM_OPT_TEST_CONTRAST_IS_SQUARED, float(_contrast_squared)
+        self.quantile = contrast_quantile is not None
+        # K of the last run's last tensor generation: set by run() only (None before the first run;
+        # tensor() does not set it -- contrast(image, q) gives the K a quantile-mode tensor() takes)
+        self.contrast_used = None
         self.desc = d
         ctx = ctypes.c_void_p()
         rc = self._L.mad_pm_create(ctypes.byref(d), ctypes.byref(ctx))
@@ -101,6 +119,11 @@ class _Context:
                      self._ctx, warn_not_converged=True, last_error=self._L.mad_pm_last_error)
         stats = st.as_dict()
         stats["converged"] = rc == C.OK
+        # K of the last tensor generation.  The attribute holds it in both modes; the dict names
+        # it where it is a result (quantile mode) and keeps its keys in absolute mode.
+        self.contrast_used = st.contrast_used
+        if self.quantile:
+            stats["contrast_used"] = st.contrast_used
         return out, stats
 
     def tensor(self, image, with_diffusivity=False):
@@ -123,6 +146,25 @@ class _Context:
             self._ctx, img.ctypes.data_as(ctypes.c_void_p), mad_dtype(img.dtype),
             G.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return G
+
+
+    def contrast(self, image, q):
+        """K = sqrt(s_q) a quantile-mode tensor generation of this image takes for the quantile q
+        (mad_pm_contrast; either contrast mode)."""
+        img = self._img(image)
+        K = ctypes.c_double()
+        self._check(self._L.mad_pm_contrast(self._ctx, img.ctypes.data_as(ctypes.c_void_p),
+                                            mad_dtype(img.dtype), float(q), ctypes.byref(K)))
+        return K.value
+
+    def select(self, values, k):
+        """The k-th smallest (0-based) of the non-negative finite values, selected on the device
+        (mad_pm_select): the same bits as np.partition(values, k)[k]."""
+        a = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        out = ctypes.c_double()
+        self._check(self._L.mad_pm_select(self._ctx, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                          a.size, int(k), ctypes.byref(out)))
+        return out.value
 
 
 class PM(_Context):
@@ -152,7 +194,9 @@ class PeronaMalikDiffusionImageFilter:
         self._device = device
         self._p = dict(diffusivity=C.PM_WEICKERT, noise_scale=0.5, contrast=1.0, exponent=2.0,
                        alpha=0.01, iterations=1, diffusion_iterations=5, cycle=C.VCYCLE,
-                       time_step=0.1, tolerance=1e-6, diffusion_iterations_per_grid=2, verbose=False)
+                       time_step=0.1, tolerance=1e-6, diffusion_iterations_per_grid=2, verbose=False,
+                       contrast_quantile=None)
+        self._contrast_used = None
         self._input = None
         self._output = None
         self.stats = None
@@ -163,7 +207,20 @@ class PeronaMalikDiffusionImageFilter:
 
     def SetDiffusivity(self, v): self._p["diffusivity"] = _diffusivity(v)
     def SetNoiseScale(self, v): self._p["noise_scale"] = float(v)
-    def SetContrast(self, v): self._p["contrast"] = float(v)
+    def SetContrast(self, v):
+        """An absolute contrast K (leaves quantile mode)."""
+        self._p["contrast"] = float(v)
+        self._p["contrast_quantile"] = None
+
+    def SetContrastQuantile(self, q):
+        """K from the q-quantile of the gradient magnitudes, per iteration (0 < q <= 1; Perona and
+        Malik: 0.9)."""
+        self._p["contrast_quantile"] = float(q)
+
+    def GetContrastUsed(self):
+        """K of the last tensor generation of the last Update (None before it)."""
+        return self._contrast_used
+
     def SetExponent(self, v): self._p["exponent"] = float(v)
     def SetAlpha(self, v): self._p["alpha"] = float(v)
     def SetIterations(self, v): self._p["iterations"] = int(v)
@@ -198,5 +255,6 @@ class PeronaMalikDiffusionImageFilter:
         finally:
             v.close()
         self.stats = stats
+        self._contrast_used = v.contrast_used
         self._output = Image(out, spacing=img.spacing, origin=img.origin)
         return self._output

@@ -3,6 +3,14 @@ measured in the same run on bench_ved.py's synthetic tube phantom.
 
     python tools/bench_pm.py [--dim 3] [--size 256] [--reps 10] [--fp64] [--md FILE]
     python tools/bench_pm.py --dim 2 [--size 8192] ...
+    python tools/bench_pm.py --quantile 0.9 [--image constant] ...
+
+--quantile Q adds a third context in the same alternation, Perona-Malik with its contrast taken
+from the Q-quantile of the gradient magnitudes (include/mad_pm.h "Contrast from a quantile"), and
+reports its tensor time and the ratio to the fixed-contrast generation; --image constant times it
+on a constant image (every key in one bin at every digit of the selection: the worst case).  Its
+algorithmic traffic: the gradient passes with s stored instead of the tensor (T per voxel), the
+selection's reads of s (two full reads, then the candidates), and the map (T in, the tensor out).
 
 Per-pass times are HIP-event times around each kernel (mad_pm_stats.pass_ms / mad_ced_stats.pass_ms)
 of whole-filter runs with one diffusion step, after one warm-up run of each filter; the two
@@ -47,6 +55,8 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--fp64", action="store_true")
     ap.add_argument("--diffusivity", default="weickert", choices=("weickert", "exponential", "rational"))
+    ap.add_argument("--quantile", type=float, default=None, help="also time quantile mode at this q")
+    ap.add_argument("--image", default="phantom", choices=("phantom", "constant"))
     ap.add_argument("--md", default=None, help="also write the result as a markdown file")
     a = ap.parse_args()
     import multigridanisotropicdiffusion_amd as M
@@ -57,19 +67,25 @@ def main():
         img = phantom(S)
     else:
         img = bench_ced.phantom_slice(S)
+    if a.image == "constant":
+        img = np.full_like(img, 100.0)
     shape, sp = (S,) * dim, (1.0,) * dim
     common = dict(noise_scale=0.5, contrast=5.0, exponent=2.0, alpha=0.01, time_step=0.1,
                   diffusion_iterations=1, precision=M.FP64 if a.fp64 else M.FP32)
     pm = (M.PM if dim == 3 else M.PM2D)(shape, sp, diffusivity=a.diffusivity, **common)
     ced = (M.CED if dim == 3 else M.CED2D)(shape, sp, enhancement="eed", feature_scale=2.0, **common)
-    for v in (pm, ced):  # warm-up: allocations, first launches
+    ctxs = [("pm", pm), ("ced", ced)]
+    if a.quantile is not None:
+        ctxs.append(("pm_quantile", (M.PM if dim == 3 else M.PM2D)(shape, sp, diffusivity=a.diffusivity,
+                                                                   **dict(common, contrast_quantile=a.quantile))))
+    for _, v in ctxs:  # warm-up: allocations, first launches
         v.run(img, out_dtype=np.float32)
-    runs = {"pm": [], "ced": []}
+    runs = {name: [] for name, _ in ctxs}
     for _ in range(a.reps):
-        for name, v in (("pm", pm), ("ced", ced)):
+        for name, v in ctxs:
             runs[name].append(v.run(img, out_dtype=np.float32)[1])
-    pm.close()
-    ced.close()
+    for _, v in ctxs:
+        v.close()
     N = float(S) ** dim
     unit = "voxel" if dim == 3 else "pixel"
     bytes_pm = sum(pm_pass_bytes(a.fp64)) if dim == 3 else 32
@@ -90,6 +106,20 @@ def main():
                      "tensor_ms_all_reps": allr}
         rows.append((name, best, B, bw))
     res["pm_over_ced"] = round(res["pm"]["tensor_ms"] / res["ced"]["tensor_ms"], 3)
+    if a.quantile is not None:
+        # s stored and re-read by the map, two full reads by the selection (the candidates on top)
+        t = 8 if a.fp64 else 4
+        Bq = bytes_pm + 4 * t
+        best, med, allr = summary(runs["pm_quantile"])
+        bw = Bq * N / (best["tensor_ms"] * 1e-3)
+        res["image"] = a.image
+        res["pm_quantile"] = {"q": a.quantile, "contrast_used": best["contrast_used"],
+                              "tensor_ms": round(best["tensor_ms"], 4), "tensor_ms_median": round(med, 4),
+                              "pass_ms": [round(x, 4) for x in best["pass_ms"]],
+                              f"bytes_per_{unit}": Bq, "tensor_TBps": round(bw / 1e12, 3),
+                              "tensor_ms_all_reps": allr}
+        res["quantile_over_fixed"] = round(best["tensor_ms"] / res["pm"]["tensor_ms"], 3)
+        res["quantile_over_fixed_median"] = round(med / res["pm"]["tensor_ms_median"], 3)
     print(json.dumps(res), flush=True)
     if not a.md:
         return
@@ -109,6 +139,12 @@ def main():
                     f"{bw / 1e12:.2f} | {bw / HBM:.1%} | {N / (best['tensor_ms'] * 1e-3) / 1e6:.0f} |\n")
         f.write(f"\nPerona-Malik takes {res['pm_over_ced']:.2f} x the EED generation's time.  All runs, ms: "
                 f"Perona-Malik {res['pm']['tensor_ms_all_reps']}, EED {res['ced']['tensor_ms_all_reps']}.\n\n")
+        if a.quantile is not None:
+            q = res["pm_quantile"]
+            f.write(f"Contrast from the {a.quantile} quantile ({a.image} image): {q['tensor_ms']:.4f} ms (median "
+                    f"{q['tensor_ms_median']:.4f}), {res['quantile_over_fixed']:.2f} x the fixed-contrast generation, "
+                    f"K = {q['contrast_used']:.6g}; pass_ms {q['pass_ms']} (the selection and the map count with the "
+                    f"last pass); all runs, ms: {q['tensor_ms_all_reps']}.\n\n")
         if dim == 3:
             f.write("| Perona-Malik pass | ms | B/voxel (algorithmic) | TB/s | of 8 TB/s |\n|---|---|---|---|---|\n")
             for pname, ms, b in zip(PM_PASSES, rows[0][1]["pass_ms"], pm_pass_bytes(a.fp64)):
