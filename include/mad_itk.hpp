@@ -20,6 +20,7 @@
 #ifndef MAD_ITK_HPP
 #define MAD_ITK_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <fstream>
@@ -469,8 +470,23 @@ class PeronaMalikDiffusionImageFilter {
   typename TOutputImage::Pointer GetOutput() const { return output_; }
   const mad_pm_stats& GetStats() const { return stats_; }
 
+  // Vector-valued images (mad_pm.h "Vector-valued images"), ITK's indexed inputs: channel c of
+  // the image is input c, its output GetOutput(c); one joint diffusivity for all.  Channels must
+  // be set without gaps from 0 and share their size.  SetInput(img) is SetInput(0, img) and
+  // GetOutput() is GetOutput(0); spacing and origin are channel 0's.
+  void SetInput(unsigned int c, const TInputImage* img) {
+    if (c == 0) input_ = img;
+    if (c > 0 && more_.size() < c) more_.resize(c, nullptr);
+    if (c > 0) more_[c - 1] = img;
+  }
+  typename TOutputImage::Pointer GetOutput(unsigned int c) const {
+    return c == 0 ? output_ : c <= more_out_.size() ? more_out_[c - 1] : nullptr;
+  }
+  unsigned int GetNumberOfChannels() const { return 1 + (unsigned int)more_.size(); }
+
   void Update() {
     if (!input_) throw Error(MAD_ERR_STATE, "SetInput first");
+    if (!more_.empty()) return UpdateChannels();
     mad_pm_desc d = desc_;
     d.dim = (int32_t)Dim;
     for (unsigned q = 0; q < 3; ++q) {
@@ -500,12 +516,54 @@ class PeronaMalikDiffusionImageFilter {
   }
 
  private:
+  // more than one channel: packs the channel buffers planar (channel c at element offset c N),
+  // sets desc.channels, and unpacks the planar output into one image per channel
+  void UpdateChannels() {
+    const unsigned C = GetNumberOfChannels();
+    const int64_t N = input_->NumberOfPixels();
+    std::vector<InputPixelType> in((size_t)(C * N));
+    for (unsigned c = 0; c < C; ++c) {
+      const TInputImage* img = c == 0 ? input_ : more_[c - 1];
+      if (!img) throw Error(MAD_ERR_STATE, "SetInput(c, image): a channel below the last one is missing");
+      if (img->GetSize() != input_->GetSize()) throw Error(MAD_ERR_INVALID, "the channels differ in size");
+      std::copy(img->GetBufferPointer(), img->GetBufferPointer() + N, in.begin() + (size_t)c * N);
+    }
+    mad_pm_desc d = desc_;
+    d.dim = (int32_t)Dim;
+    d.channels = (int32_t)C;
+    for (unsigned q = 0; q < 3; ++q) {
+      d.size[q] = q < Dim ? input_->GetSize()[q] : 1;
+      d.spacing[q] = q < Dim ? input_->GetSpacing()[q] : 1.0;
+    }
+    d.smoother = TSmootherType::id;
+    mad_pm_destroy(ctx_);
+    ctx_ = nullptr;
+    if (int rc = mad_pm_create(&d, &ctx_))
+      throw Error(rc, std::string("mad_pm: ") + mad_pm_last_error(nullptr));
+    std::vector<OutputPixelType> out((size_t)(C * N));
+    const int rc = mad_pm_run(ctx_, in.data(), itkshim::PixelTraits<InputPixelType>::id, out.data(),
+                              itkshim::PixelTraits<OutputPixelType>::id, &stats_);
+    converged_ = check_run(rc, "mad_pm", mad_pm_last_error(ctx_));  // throws unless the output is written
+    more_out_.assign(C - 1, nullptr);
+    for (unsigned c = 0; c < C; ++c) {
+      auto o = TOutputImage::New();
+      o->SetRegions(input_->GetSize());
+      o->Allocate();
+      o->SetSpacing(input_->GetSpacing());
+      o->SetOrigin(input_->GetOrigin());
+      std::copy(out.begin() + (size_t)c * N, out.begin() + (size_t)(c + 1) * N, o->GetBufferPointer());
+      (c == 0 ? output_ : more_out_[c - 1]) = o;
+    }
+  }
+
   mad_pm_desc desc_{};
   mad_pm_ctx* ctx_ = nullptr;
   mad_pm_stats stats_{};
   bool converged_ = true;
   const TInputImage* input_ = nullptr;
   typename TOutputImage::Pointer output_;
+  std::vector<const TInputImage*> more_;                    // channels 1..
+  std::vector<typename TOutputImage::Pointer> more_out_;
 };
 
 }  // namespace mad

@@ -47,6 +47,31 @@
  * mad_pm_contrast and mad_pm_select, are declared in mad_pm_quantile.h.  See DESIGN.md
  * "Contrast from a quantile" and tests/pm_quantile_numpy.py.
  *
+ * Vector-valued images (channels = C > 1; Gerig et al. 1992): one diffusivity from the summed
+ * squared gradients of all channels, g(sum_c |grad u_c,sigma|^2), applied to every channel.
+ *   layout every image argument of the entry points below is planar: C arrays of
+ *          N = size[0] size[1] size[2] elements, channel c at element offset c N, input and output
+ *          alike.  channels = 0 is read as 1; anything outside 1..16 is MAD_ERR_INVALID from
+ *          mad_pm_create, before a device is touched.
+ *   1.     per channel, exactly as above
+ *   2.     s_c = gx_c gx_c + gy_c gy_c (+ gz_c gz_c) as above, then s = s_0 + s_1 + ... + s_{C-1},
+ *          summed left to right in the storage precision with contraction off, then taken to
+ *          fp64.  With C = 1 this is the s of step 2 bit for bit.
+ *   3.-4.  on the joint s.  Quantile mode selects among the N values of the joint s, and
+ *          contrast_used is sqrt(s_q) of the joint s.
+ *   5.     per outer iteration: one tensor generation from all current channels, one solver
+ *          setup, then every channel through diffusion_iterations implicit steps with the same
+ *          operators.
+ *   stats  total_cycles sums over the channels, last_relres is the largest of the channels'
+ *          last-step values in the last iteration, stalled the OR over the channels, diffusion_ms
+ *          covers all channels; MAD_ERR_NOT_CONVERGED as for one channel.  3D: the z and y passes
+ *          alternate per channel, so pass_ms[0] is the first channel's z pass and pass_ms[1] every
+ *          pass between it and the x pass.
+ *   mad_pm_tensor returns the joint tensor and the joint g; mad_pm_gradient writes C dim arrays of
+ *   N, channel slowest and (gx, gy(, gz)) within a channel; mad_pm_contrast gives the joint K;
+ *   mad_pm_select is unchanged.  See DESIGN.md "Vector-valued images" and
+ *   tests/pm_vector_numpy.py.
+ *
  * Limit on sigma.  Every kernel keeps its tile and the taps' halo in 128 KiB of LDS and shrinks
  * the tile for long taps; taps that do not fit the smallest tile make mad_pm_run,
  * mad_pm_tensor and mad_pm_gradient return MAD_ERR_UNSUPPORTED ("Gaussian taps too long for
@@ -120,7 +145,13 @@ typedef struct mad_pm_desc {
   int32_t dim;                     /* 3 (default; 0 is read as 3) or 2; anything else is invalid */
   int32_t contrast_mode;           /* mad_pm_contrast_mode, MAD_PM_CONTRAST_ABSOLUTE (the word was
                                       reserved[0], which every earlier caller left 0) */
-  int32_t reserved[3];
+  union {
+    int32_t channels;              /* C, 1..16 (0 is read as 1): planar vector-valued images with one
+                                      joint diffusivity, "Vector-valued images" above.  The word is the
+                                      first of the three reserved ones, which every earlier caller left
+                                      0; `reserved` stays where it was and names it too */
+    int32_t reserved[3];           /* [0] is channels; [1..2] stay 0 */
+  };
 } mad_pm_desc;
 
 typedef struct mad_pm_stats {
@@ -141,7 +172,7 @@ typedef struct mad_pm_stats {
   int32_t reserved[2];
 } mad_pm_stats;
 
-/* the layout did not move: contrast_mode took reserved[0]; contrast_used, behind 4 bytes of
+/* the layout did not move: contrast_mode took reserved[0] of four, channels the next; contrast_used, behind 4 bytes of
  * padding, took the stats' reserved[0..2] */
 #if defined(__cplusplus)
 static_assert(sizeof(mad_pm_desc) == 176 && sizeof(mad_pm_stats) == 88, "mad_pm.h layout");

@@ -230,11 +230,17 @@ class CedStats(ctypes.Structure):
         return d
 
 
+class _PmDescTailNamed(ctypes.Structure):
+    _fields_ = [("contrast_mode", ctypes.c_int32), ("channels", ctypes.c_int32)]
+
+
 class _PmDescTail(ctypes.Union):
-    """The last four words of mad_pm_desc: contrast_mode took the first reserved word.  `reserved`
-    stays the four-word view bindings of the earlier layout read (word 0 is contrast_mode, 0 =
-    absolute in every descriptor written before the mode existed)."""
-    _fields_ = [("contrast_mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+    """The last four words of mad_pm_desc: contrast_mode took the first reserved word, channels the
+    second.  `reserved` stays the four-word view bindings of the earlier layout read (word 0 is
+    contrast_mode, 0 = absolute, word 1 is channels, 0 = one channel, in every descriptor written
+    before they existed)."""
+    _anonymous_ = ("_named",)
+    _fields_ = [("_named", _PmDescTailNamed), ("reserved", ctypes.c_int32 * 4)]
 
 
 class PmDesc(ctypes.Structure):

@@ -16,9 +16,11 @@ struct mad_pm_ctx {
   int tile[2] = {0, 0};    // 2D: the output tile of the last tensor generation (x, y)
   int64_t n[3] = {0, 0, 0};
   int64_t N = 0;
-  double* img = nullptr;   // internal image (fp64)
-  double* img2 = nullptr;  // next iterate
-  void* vol = nullptr;     // 3D: 5 scratch volumes in the storage precision
+  int C = 1;               // channels (mad_pm_desc.channels, 0 read as 1); images are C planes of N
+  double* img = nullptr;   // internal image (fp64), C N
+  double* img2 = nullptr;  // next iterate, C N
+  void* vol = nullptr;     // 3D: 3 C + 2 scratch volumes in the storage precision (C = 1: the 5 of
+                           // the scalar passes)
   void* taps = nullptr;    // device taps, per axis [K0 | K1 | 0 0 0 K0 0 0 0 | 0 0 0 K1 0 0 0]
   int R[3] = {0, 0, 0};
   size_t tap_off[3] = {0, 0, 0};  // element offset of each axis' taps
@@ -65,17 +67,18 @@ void* pm_stage(mad_pm_ctx* v, size_t bytes) {
   return v->stage;
 }
 
-// host or device image (any dtype) -> v->img (fp64)
+// host or device image (any dtype, all C planes) -> v->img (fp64)
 void pm_load_image(mad_pm_ctx* v, const void* src, int dt, bool dev) {
   const size_t es = dtype_size(dt);
   REQUIRE(es, MAD_ERR_INVALID, "bad image dtype");
   hipStream_t st = v->mad->stream;
+  const int64_t n = v->C * v->N;
   if (!dev) {
-    void* s = pm_stage(v, es * v->N);
-    HIP_CHECK(hipMemcpyAsync(s, src, es * v->N, hipMemcpyHostToDevice, st));
+    void* s = pm_stage(v, es * n);
+    HIP_CHECK(hipMemcpyAsync(s, src, es * n, hipMemcpyHostToDevice, st));
     src = s;
   }
-  convert_to<double>(src, dt, v->img, v->N, st);
+  convert_to<double>(src, dt, v->img, n, st);
 }
 
 // allow the new kernels more than the default 64 KiB of dynamic LDS (once per type)
@@ -85,7 +88,10 @@ void pm_lds_attr() {
   if (done) return;
   for (const void* k : {(const void*)pm_x_k<T, PM_TENSOR>, (const void*)pm_x_k<T, PM_GRADIENT>,
                         (const void*)pm_x_k<T, PM_SQNORM>, (const void*)pm2_k<T, PM_TENSOR>,
-                        (const void*)pm2_k<T, PM_GRADIENT>, (const void*)pm2_k<T, PM_SQNORM>})
+                        (const void*)pm2_k<T, PM_GRADIENT>, (const void*)pm2_k<T, PM_SQNORM>,
+                        (const void*)pmv_x_k<T, PM_TENSOR>, (const void*)pmv_x_k<T, PM_GRADIENT>,
+                        (const void*)pmv_x_k<T, PM_SQNORM>, (const void*)pm2v_k<T, PM_TENSOR>,
+                        (const void*)pm2v_k<T, PM_GRADIENT>, (const void*)pm2v_k<T, PM_SQNORM>})
     HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVedLds));
   done = true;
 }
@@ -189,7 +195,8 @@ void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, E
   const size_t l3 = lds_for(256 + 2 * R[0], 1, 3);
   REQUIRE(l1 <= kVedLds && l2 <= kVedLds && l3 <= kVedLds, MAD_ERR_UNSUPPORTED,
           "Gaussian taps too long for the LDS tiles (scale / spacing too large)");
-  if (!v->vol) HIP_CHECK(big_alloc((void**)&v->vol, sizeof(T) * 5 * N));
+  const int C = v->C;
+  if (!v->vol) HIP_CHECK(big_alloc((void**)&v->vol, sizeof(T) * (3 * C + 2) * N));
   T* sq = q > 0.0 ? pm_sq<T>(v) : nullptr;
   T* f = (T*)v->vol;
   T *z0 = f, *z1 = f + N, *a00 = f + 2 * N, *a10 = f + 3 * N, *a01 = f + 4 * N;
@@ -200,6 +207,34 @@ void pm_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, E
   const T ihx = (T)(1.0 / h[0]), ihy = (T)(1.0 / h[1]), ihz = (T)(1.0 / h[2]);
   const PmParams pp = pm_params(v);
   if (ev) HIP_CHECK(hipEventRecord(ev[0], st));
+  if (C > 1) {
+    // vector-valued: z and y passes per channel through the one pair z0, z1 into the channel's
+    // three pass-2 volumes, then the joint x pass.  ev[1] follows the first channel's z pass:
+    // pass_ms[1] holds every pass between it and the x pass.
+    for (int ch = 0; ch < C; ++ch) {
+      T* a = a00 + (int64_t)(3 * ch) * N;
+      hipLaunchKernelGGL((ced_z_k<T>), dim3((nx + 63) / 64, (ny + 3) / 4, (nz + ZT - 1) / ZT), dim3(256), l1, st,
+                         v->img + (int64_t)ch * N, z0, z1, tp + v->tap_off[2], R[2], nx, ny, nz, ZT);
+      if (ev && ch == 0) HIP_CHECK(hipEventRecord(ev[1], st));
+      hipLaunchKernelGGL((ced_y_k<T>), dim3((nx + 63) / 64, (ny + YT - 1) / YT, nz), dim3(256), l2, st, z0, z1,
+                         a, a + N, a + 2 * N, tp + v->tap_off[1], R[1], nx, ny, nz, YT);
+    }
+    if (ev) HIP_CHECK(hipEventRecord(ev[2], st));
+    const dim3 g3((nx + 255) / 256, ny, nz);
+    if (mode == PM_GRADIENT) {
+      hipLaunchKernelGGL((pmv_x_k<T, PM_GRADIENT>), g3, dim3(256), l3, st, a00, C, N, tp + v->tap_off[0], R[0], nx,
+                         ny, nz, ihx, ihy, ihz, cs, D, nullptr, pp);
+    } else if (sq) {
+      hipLaunchKernelGGL((pmv_x_k<T, PM_SQNORM>), g3, dim3(256), l3, st, a00, C, N, tp + v->tap_off[0], R[0], nx,
+                         ny, nz, ihx, ihy, ihz, cs, (double*)sq, nullptr, pp);
+      pm_select_and_map<T>(v, q, mode == PM_TENSOR ? D : nullptr, cs, gout);
+    } else
+      hipLaunchKernelGGL((pmv_x_k<T, PM_TENSOR>), g3, dim3(256), l3, st, a00, C, N, tp + v->tap_off[0], R[0], nx,
+                         ny, nz, ihx, ihy, ihz, cs, D, gout, pp);
+    if (ev) HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   hipLaunchKernelGGL((ced_z_k<T>), dim3((nx + 63) / 64, (ny + 3) / 4, (nz + ZT - 1) / ZT), dim3(256), l1, st,
                      v->img, z0, z1, tp + v->tap_off[2], R[2], nx, ny, nz, ZT);
   if (ev) HIP_CHECK(hipEventRecord(ev[1], st));
@@ -267,7 +302,20 @@ void pm2_generate(mad_pm_ctx* v, int mode, double* D, int64_t cs, double* gout, 
   const dim3 grid((nx + TW - 1) / TW, (ny + TH - 1) / TH);
   const int s1 = pm2_lds(TW, TH, R).s1;
   if (ev) HIP_CHECK(hipEventRecord(ev[0], st));
-  if (mode == PM_GRADIENT) {
+  const int C = v->C;
+  if (C > 1) {
+    // vector-valued: the channel loop runs inside the kernel, on the same tile and LDS
+    if (mode == PM_GRADIENT) {
+      hipLaunchKernelGGL((pm2v_k<T, PM_GRADIENT>), grid, dim3(256), lds, st, v->img, C, v->N, txp, ty, R[0], R[1],
+                         nx, ny, TW, TH, s1, ihx, ihy, cs, D, nullptr, pp);
+    } else if (sq) {
+      hipLaunchKernelGGL((pm2v_k<T, PM_SQNORM>), grid, dim3(256), lds, st, v->img, C, v->N, txp, ty, R[0], R[1], nx,
+                         ny, TW, TH, s1, ihx, ihy, cs, (double*)sq, nullptr, pp);
+      pm_select_and_map<T>(v, q, mode == PM_TENSOR ? D : nullptr, cs, gout);
+    } else
+      hipLaunchKernelGGL((pm2v_k<T, PM_TENSOR>), grid, dim3(256), lds, st, v->img, C, v->N, txp, ty, R[0], R[1], nx,
+                         ny, TW, TH, s1, ihx, ihy, cs, D, gout, pp);
+  } else if (mode == PM_GRADIENT) {
     hipLaunchKernelGGL((pm2_k<T, PM_GRADIENT>), grid, dim3(256), lds, st, v->img, txp, ty, R[0], R[1], nx, ny,
                        TW, TH, s1, ihx, ihy, cs, D, nullptr, pp);
   } else if (sq) {
@@ -321,8 +369,16 @@ void pm_run_impl(mad_pm_ctx* v, const void* in, int in_dt, void* out, int out_dt
   for (uint32_t it = 0; it < v->d.iterations; ++it) {
     if (v->d.verbose) std::printf("Iteration n.%u...\n", it + 1);
     pm_tensor_to_solver(v, nullptr, ev);
+    // every channel through the same operators: the first run_impl does the setup
+    // (pm_tensor_to_solver cleared setup_done), the others find it done
     mad_stats ms{};
-    mad_call(c, run_impl(c, v->img, MAD_F64, v->img2, MAD_F64, &ms, true));
+    for (int ch = 0; ch < v->C; ++ch) {
+      mad_stats cs{};
+      mad_call(c, run_impl(c, v->img + (int64_t)ch * v->N, MAD_F64, v->img2 + (int64_t)ch * v->N, MAD_F64, &cs, true));
+      ms.total_cycles += cs.total_cycles;
+      ms.last_relres = ch ? std::max(ms.last_relres, cs.last_relres) : cs.last_relres;
+      ms.stalled |= cs.stalled;
+    }
     std::swap(v->img, v->img2);
     HIP_CHECK(hipEventRecord(done, c->stream));
     HIP_CHECK(hipEventSynchronize(done));
@@ -333,9 +389,10 @@ void pm_run_impl(mad_pm_ctx* v, const void* in, int in_dt, void* out, int out_dt
     relres = ms.last_relres;
     stalled |= ms.stalled;
   }
-  void* dst = dev ? out : pm_stage(v, oes * v->N);
-  convert_from<double>(v->img, dst, out_dt, v->N, c->stream);
-  if (!dev) HIP_CHECK(hipMemcpyAsync(out, dst, oes * v->N, hipMemcpyDeviceToHost, c->stream));
+  const int64_t cn = v->C * v->N;
+  void* dst = dev ? out : pm_stage(v, oes * cn);
+  convert_from<double>(v->img, dst, out_dt, cn, c->stream);
+  if (!dev) HIP_CHECK(hipMemcpyAsync(out, dst, oes * cn, hipMemcpyDeviceToHost, c->stream));
   HIP_CHECK(hipStreamSynchronize(c->stream));
   if (st) {
     std::memset(st, 0, sizeof(*st));
@@ -406,6 +463,8 @@ int mad_pm_create(const mad_pm_desc* d, mad_pm_ctx** out) {
     REQUIRE(d->noise_scale > 0.0, MAD_ERR_INVALID, "noise_scale must be positive");
     REQUIRE(d->contrast_mode == MAD_PM_CONTRAST_ABSOLUTE || d->contrast_mode == MAD_PM_CONTRAST_QUANTILE,
             MAD_ERR_INVALID, "unknown contrast_mode (MAD_PM_CONTRAST_ABSOLUTE or MAD_PM_CONTRAST_QUANTILE)");
+    REQUIRE(d->channels >= 0 && d->channels <= 16, MAD_ERR_INVALID,
+            "channels must lie in 1..16 (0 is read as 1)");
     const bool quantile = d->contrast_mode == MAD_PM_CONTRAST_QUANTILE;
     if (quantile)
       REQUIRE(d->contrast > 0.0 && d->contrast <= 1.0, MAD_ERR_INVALID,
@@ -435,6 +494,7 @@ int mad_pm_create(const mad_pm_desc* d, mad_pm_ctx** out) {
     v->d = *d;
     v->dim = dim;
     v->quantile = quantile;
+    v->C = d->channels == 0 ? 1 : d->channels;
     mad_desc md;
     mad_desc_init(&md);
     md.dim = dim;
@@ -462,8 +522,8 @@ int mad_pm_create(const mad_pm_desc* d, mad_pm_ctx** out) {
     REQUIRE(v->n[0] <= INT32_MAX - 1024 && v->n[1] <= 65535 && v->n[2] <= 65535, MAD_ERR_INVALID,
             "image too large for the gradient passes' grid mapping");
     HIP_CHECK(hipSetDevice(v->mad->device));
-    HIP_CHECK(big_alloc((void**)&v->img, sizeof(double) * v->N));
-    HIP_CHECK(big_alloc((void**)&v->img2, sizeof(double) * v->N));
+    HIP_CHECK(big_alloc((void**)&v->img, sizeof(double) * v->C * v->N));
+    HIP_CHECK(big_alloc((void**)&v->img2, sizeof(double) * v->C * v->N));
     if (d->precision == MAD_FP64) pm_upload_taps<double>(v.get());
     else pm_upload_taps<float>(v.get());
   });
@@ -515,11 +575,11 @@ int mad_pm_gradient(mad_pm_ctx* v, const void* image, int32_t dtype, double* gra
     HIP_CHECK(hipSetDevice(v->mad->device));
     pm_load_image(v, image, dtype, false);
     double* G = nullptr;
-    HIP_CHECK(big_alloc((void**)&G, sizeof(double) * v->dim * v->N));
+    const size_t gbytes = sizeof(double) * v->C * v->dim * v->N;  // channel slowest
+    HIP_CHECK(big_alloc((void**)&G, gbytes));
     std::unique_ptr<double, void (*)(double*)> hold(G, [](double* p) { (void)hipFree(p); });
     pm_generate_any(v, PM_GRADIENT, G, v->N, nullptr, nullptr);
-    HIP_CHECK(hipMemcpyAsync(grad_soa, G, sizeof(double) * v->dim * v->N, hipMemcpyDeviceToHost,
-                             v->mad->stream));
+    HIP_CHECK(hipMemcpyAsync(grad_soa, G, gbytes, hipMemcpyDeviceToHost, v->mad->stream));
     HIP_CHECK(hipStreamSynchronize(v->mad->stream));
   });
 }

@@ -14,6 +14,8 @@
 // Quantile mode (contrast from a gradient quantile) splits the last step: pm_x_k / pm2_k in the
 // mode PM_SQNORM store s alone (T per voxel), mad_select.hpp selects s_q, and pm_map_k maps
 // s -> g -> D with K^2 = s_q read from device memory.
+// Vector-valued images (C > 1 channels, one joint diffusivity) take pmv_x_k / pm2v_k at the end of
+// this file in place of pm_x_k / pm2_k: 48 C + 48 B per voxel (fp32), 8 C + 24 B per pixel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -290,6 +292,265 @@ __global__ void __launch_bounds__(256) pm2_k(const double* __restrict__ in, cons
       continue;
     }
     const double gv = pm_diffusivity((double)s, pp);
+    D[p] = gv;
+    D[cs + p] = 0.0;
+    D[2 * cs + p] = gv;
+    if (gout) gout[p] = gv;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// Vector-valued images (mad_pm_desc.channels = C > 1; include/mad_pm.h "Vector-valued images"):
+// one diffusivity from the summed squared gradients of all channels, s = s_0 + ... + s_{C-1},
+// summed left to right in T.  The image is planar, channel c at element offset c N.  The scalar
+// kernels above stay as they are (C = 1 launches them); the two below repeat their phases inside
+// a channel loop rather than share code with them, so the scalar kernels' code does not move.
+//
+// 3D: ced_z_k and ced_y_k run per channel into three pass-2 volumes per channel, a = [a00_0,
+// a10_0, a01_0, a00_1, ...] (each N elements); this x pass stages one channel's three rows at a
+// time, keeps the voxel's running s in a register, and maps and stores once after the last
+// channel: 3 C T in, 48 out (fp32 with the two passes before it: 48 C + 48 B per voxel, against
+// 96 C for C scalar generations).  No thread leaves before the last barrier: a thread with
+// i >= nx stages and waits with the others and skips the arithmetic and the stores.  The barrier
+// at the head of channels 1.. keeps a channel's rows until every thread has read its taps.
+// PM_GRADIENT: D = 3 C arrays, channel slowest, (gx, gy, gz) within a channel.
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) pmv_x_k(const T* __restrict__ a, int C, int64_t N,
+                                               const T* __restrict__ taps, int R, int nx, int ny, int nz,
+                                               T ihx, T ihy, T ihz, int64_t cs, double* __restrict__ D,
+                                               double* __restrict__ gout, PmParams pp) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char ved_smem[];
+  T* L = reinterpret_cast<T*>(ved_smem);
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * 256;
+  const int i = x0 + tid;
+  const bool live = i < nx;
+  const int64_t row = ((int64_t)blockIdx.z * ny + blockIdx.y) * nx;
+  const int64_t p = row + i;
+  const int nw = 256 + 2 * R;
+  const int W = 2 * R + 1;
+  T s = T(0);
+  for (int ch = 0; ch < C; ++ch) {
+    const T* a00 = a + (int64_t)(3 * ch) * N;
+    const T* a10 = a00 + N;
+    const T* a01 = a10 + N;
+    if (ch) __syncthreads();
+    for (int e = tid; e < nw; e += 256) {
+      const int64_t q = row + min(max(x0 - R + e, 0), nx - 1);
+      L[e] = a00[q];
+      L[nw + e] = a10[q];
+      L[2 * nw + e] = a01[q];
+    }
+    __syncthreads();
+    if (live) {
+      const T* c = L + tid;
+      T gx = T(0), gy = T(0), gz = T(0);
+#pragma unroll 4
+      for (int q = 0; q < W; ++q) {
+        const T k0 = taps[q], k1 = taps[W + q];
+        gx = fma(k1, c[q], gx);
+        gy = fma(k0, c[nw + q], gy);
+        gz = fma(k0, c[2 * nw + q], gz);
+      }
+      gx = gx * ihx;
+      gy = gy * ihy;
+      gz = gz * ihz;
+      if (MODE == PM_GRADIENT) {
+        double* G = D + (int64_t)(3 * ch) * cs;
+        G[p] = (double)gx;
+        G[cs + p] = (double)gy;
+        G[2 * cs + p] = (double)gz;
+      } else {
+        T sc = gx * gx;
+        sc = sc + gy * gy;
+        sc = sc + gz * gz;
+        s = ch ? s + sc : sc;
+      }
+    }
+  }
+  if (MODE == PM_GRADIENT || !live) return;
+  if (MODE == PM_SQNORM) {
+    reinterpret_cast<T*>(D)[p] = s;
+    return;
+  }
+  const double g = pm_diffusivity((double)s, pp);
+  D[p] = g;
+  D[cs + p] = 0.0;
+  D[2 * cs + p] = 0.0;
+  D[3 * cs + p] = g;
+  D[4 * cs + p] = 0.0;
+  D[5 * cs + p] = g;
+  if (gout) gout[p] = g;
+}
+
+// 2D: pm2_k's phases A-D inside a channel loop, on pm2_k's LDS regions (the same tile plan).  in
+// holds C planes of N = nx ny pixels.  Phase D of a channel adds its s_c to the running s of the
+// tile's pixels, which stays in registers: TW TH <= 2048 over 256 threads is at most
+// PM2V_ACC = 8 pixels per thread, item e = tid + 256 j, in a loop of that compile-time bound.
+// After the last channel the same items map and store: 8 C in, 24 out per pixel, against 32 C.
+// Phase D of channel c reads gx, gy from R1, which phase A of channel c + 1 overwrites: the
+// barrier at the head of channels 1.. stands between them.  PM_GRADIENT: D = 2 C arrays, channel
+// slowest, (gx, gy) within a channel.
+// Scalar registers: inside the loop every phase's tile constants would stay live over all four
+// phases (the compiler hoists them out of the channel loop), about forty wave-uniform values
+// over the kernel's arguments, more than the 102 scalar registers hold.  Each phase therefore
+// derives its constants anew from opaque copies of (Rx, Ry, TW, TH) (pm_fresh), a few scalar
+// instructions per phase and channel, and after the last channel the running s goes through
+// each thread's own slots of R2 (dead by then) so that the map runs once, in a rolled loop.
+enum { PM2V_ACC = 8 };
+
+// a copy of a wave-uniform value the compiler cannot trace to its source: what is computed from
+// it is computed where it stands, not hoisted out of the enclosing loop
+__device__ inline int pm_fresh(int v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+template <typename T, int MODE>
+__global__ void __launch_bounds__(256) pm2v_k(const double* __restrict__ in, int C, int64_t N,
+                                              const T* __restrict__ taps_xp, const T* __restrict__ taps_y,
+                                              int Rx, int Ry, int nx, int ny, int TW, int TH, int S1, T ihx,
+                                              T ihy, int64_t cs, double* __restrict__ D,
+                                              double* __restrict__ gout, PmParams pp) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char ved_smem[];
+  T* R1 = reinterpret_cast<T*>(ved_smem);
+  T* R2 = R1 + S1;
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+  T s[PM2V_ACC];
+#pragma unroll
+  for (int j = 0; j < PM2V_ACC; ++j) s[j] = T(0);
+  for (int ch = 0; ch < C; ++ch) {
+    const double* u0 = in + (int64_t)ch * N;
+    if (ch) __syncthreads();
+    {  // A: eight loads in flight per thread
+      const int rx = pm_fresh(Rx), ry = pm_fresh(Ry);
+      const int WA = pm_fresh(TW) + 2 * rx, HA = pm_fresh(TH) + 2 * ry;  // staged image
+      const float iWA = 1.0f / (float)WA;
+      const int nA = WA * HA;
+      for (int e0 = tid; e0 < nA; e0 += 2048) {
+        double u[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int e = min(e0 + 256 * j, nA - 1);
+          const int r = ced2_div(e, iWA), c = e - r * WA;
+          const int yy = min(max(y0 - ry + r, 0), ny - 1), xx = min(max(x0 - rx + c, 0), nx - 1);
+          u[j] = u0[(int64_t)yy * nx + xx];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (e0 + 256 * j < nA) R1[e0 + 256 * j] = (T)u[j];
+      }
+    }
+    __syncthreads();
+    {  // B: item = (staged column c, rows 4 g .. 4 g + 3); lanes run along c
+      const int th = pm_fresh(TH);
+      const int WA = pm_fresh(TW) + 2 * pm_fresh(Rx), PB = th + 1, Wy = 2 * pm_fresh(Ry) + 1;
+      const float iWA = 1.0f / (float)WA;
+      const int SB = WA * PB;
+      for (int e = tid; e < WA * (th / 4); e += 256) {
+        const int g = ced2_div(e, iWA), c = e - g * WA;
+        const T* a[4];
+        T b0[4], b1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int p = min(y0 + 4 * g + j, ny - 1);
+          a[j] = R1 + (p - y0) * WA + c;
+          b0[j] = b1[j] = T(0);
+        }
+#pragma unroll 2
+        for (int q = 0; q < Wy; ++q) {
+          const T k0 = taps_y[q], k1 = taps_y[Wy + q];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const T v = a[j][q * WA];
+            b0[j] = fma(k0, v, b0[j]);
+            b1[j] = fma(k1, v, b1[j]);
+          }
+        }
+        T* o = R2 + c * PB + 4 * g;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[j] = b0[j];
+          o[SB + j] = b1[j];
+        }
+      }
+    }
+    __syncthreads();
+    {  // C: item = (row rb, four consecutive tile columns i0..i0+3); lanes run along rb
+      const int tw = pm_fresh(TW), th = pm_fresh(TH), rx = pm_fresh(Rx);
+      const int PB = th + 1, PC = tw + 1, Wx = 2 * rx + 1;
+      const int SB = (tw + 2 * rx) * PB, SC = th * PC;
+      const T* k0p = taps_xp;  // the padded taps: tap t at [3 + R + t]
+      const T* k1p = taps_xp + Wx + 6;
+      const float iTH = 1.0f / (float)th;
+      for (int e = tid; e < th * (tw / 4); e += 256) {
+        const int g = ced2_div(e, iTH), rb = e - g * th, i0 = 4 * g;
+        const T* c = R2 + i0 * PB + rb;
+        T gx[4], gy[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gx[j] = gy[j] = T(0);
+#pragma unroll 2
+        for (int r = 0; r < Wx + 3; ++r) {
+          const T v0 = c[r * PB], v1 = c[SB + r * PB];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            gx[j] = fma(k1p[3 + r - j], v0, gx[j]);
+            gy[j] = fma(k0p[3 + r - j], v1, gy[j]);
+          }
+        }
+        T* o = R1 + rb * PC + i0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[j] = gx[j] * ihx;
+          o[SC + j] = gy[j] * ihy;
+        }
+      }
+    }
+    __syncthreads();
+    {  // D: one pixel per item; lanes run along x.  The channel's s_c joins the running s.
+      const int tw = pm_fresh(TW), th = pm_fresh(TH);
+      const int PC = tw + 1, SC = th * PC, sh = __ffs(tw) - 1, nD = tw * th;
+#pragma unroll
+      for (int j = 0; j < PM2V_ACC; ++j) {
+        const int e = tid + 256 * j;
+        if (e >= nD) continue;
+        const int xi = e & (tw - 1), o = e >> sh;
+        const T gx = R1[o * PC + xi], gy = R1[SC + o * PC + xi];
+        if (MODE == PM_GRADIENT) {
+          const int i = x0 + xi, y = y0 + o;
+          if (i >= nx || y >= ny) continue;
+          const int64_t p = (int64_t)y * nx + i;
+          double* G = D + (int64_t)(2 * ch) * cs;
+          G[p] = (double)gx;
+          G[cs + p] = (double)gy;
+          continue;
+        }
+        T sc = gx * gx;
+        sc = sc + gy * gy;
+        s[j] = ch ? s[j] + sc : sc;
+      }
+    }
+  }
+  if (MODE == PM_GRADIENT) return;
+  // the map: each thread's s through its own slots of R2, last read by phase C before a barrier
+  const int sh = __ffs(TW) - 1, nD = TW * TH;
+#pragma unroll
+  for (int j = 0; j < PM2V_ACC; ++j)
+    if (tid + 256 * j < nD) R2[tid + 256 * j] = s[j];
+  for (int e = tid; e < nD; e += 256) {
+    const int xi = e & (TW - 1), o = e >> sh;
+    const int i = x0 + xi, y = y0 + o;
+    if (i >= nx || y >= ny) continue;
+    const T sv = R2[e];
+    const int64_t p = (int64_t)y * nx + i;
+    if (MODE == PM_SQNORM) {
+      reinterpret_cast<T*>(D)[p] = sv;
+      continue;
+    }
+    const double gv = pm_diffusivity((double)sv, pp);
     D[p] = gv;
     D[cs + p] = 0.0;
     D[2 * cs + p] = gv;

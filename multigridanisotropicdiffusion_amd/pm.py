@@ -12,7 +12,10 @@ The solver's stencil keeps the maximum principle where the diffusivity varies ge
 or a larger alpha keep it (include/mad_pm.h, "Monotonicity").
 
 ``PM`` is the low-level context (one image size) for volumes, ``PM2D`` the same for 2D images
-(one fused tensor kernel); ``PeronaMalikDiffusionImageFilter`` the ITK-shaped facade.
+(one fused tensor kernel); ``PeronaMalikDiffusionImageFilter`` the ITK-shaped facade.  All three
+take vector-valued images (``channels=C``, ``SetInput(image, channel_axis=...)``): colour pictures
+and multi-echo volumes with one joint diffusivity from the summed squared gradients of all
+channels, so an edge that one channel shows clearly is kept in every channel.
 """
 import ctypes
 
@@ -43,7 +46,11 @@ class _Context:
     attribute contrast_used holds the K of the last run in both modes: run sets it, it is None
     before the first run, and 0.0 after a quantile-mode run with iterations = 0 (no generation).
     _contrast_squared is for tests only: an absolute K^2 fed to the map unsquared
-    (MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED)."""
+    (MAD_PM_OPT_TEST_CONTRAST_IS_SQUARED).
+    channels=C > 1: vector-valued images with one joint diffusivity (include/mad_pm.h,
+    "Vector-valued images").  Images are (C,) + shape, or with run's channel_axis=-1 shape + (C,);
+    tensor() returns the joint tensor, gradient() (C, dim) + shape, and run's stats dict adds
+    "channels"."""
 
     DIM = None
 
@@ -51,12 +58,15 @@ class _Context:
                  exponent=2.0, alpha=0.01, iterations=1, diffusion_iterations=5, cycle=C.VCYCLE,
                  time_step=0.1, tolerance=1e-6, diffusion_iterations_per_grid=2, verbose=False,
                  smoother=C.GAUSS_SEIDEL, precision=C.PRECISION_AUTO, device=-1, contrast_quantile=None,
-                 _contrast_squared=None):
+                 channels=1, _contrast_squared=None):
         dim = self.DIM
         if len(shape) != dim:
             raise ValueError(f"{type(self).__name__} takes a {dim}D shape (PM: volumes, PM2D: images)")
         self._L = C.load()
         self.shape = tuple(int(v) for v in shape)
+        self.channels = int(channels)
+        # the shape of an image argument: one channel keeps the plain shape
+        self.image_shape = self.shape if self.channels == 1 else (self.channels,) + self.shape
         self.ncomp = dim * (dim + 1) // 2
         d = C.PmDesc()
         C.check(self._L.mad_pm_desc_init(ctypes.byref(d)))
@@ -79,6 +89,7 @@ class _Context:
             d.contrast_mode, d.contrast = C.PM_CONTRAST_QUANTILE, float(contrast_quantile)
         elif _contrast_squared is not None:
             d.options, d.contrast = C.PM_OPT_TEST_CONTRAST_IS_SQUARED, float(_contrast_squared)
+        d.channels = self.channels
         self.quantile = contrast_quantile is not None
         # K of the last run's last tensor generation: set by run() only (None before the first run;
         # tensor() does not set it -- contrast(image, q) gives the K a quantile-mode tensor() takes)
@@ -104,14 +115,19 @@ class _Context:
 
     def _img(self, image):
         img = np.ascontiguousarray(image)
-        if img.shape != self.shape:
-            raise ValueError(f"image shape {img.shape} != {self.shape}")
+        if img.shape != self.image_shape:
+            raise ValueError(f"image shape {img.shape} != {self.image_shape}")
         return img
 
-    def run(self, image, out_dtype=np.float64):
-        """The whole filter on a host image; returns (output, stats dict)."""
-        img = self._img(image)
-        out = np.empty(self.shape, dtype=out_dtype)
+    def run(self, image, out_dtype=np.float64, channel_axis=0):
+        """The whole filter on a host image; returns (output, stats dict).  channels > 1:
+        channel_axis=0 takes (C,) + shape, channel_axis=-1 pictures of shape + (C,) (made planar
+        on the host); the output comes back in the layout it was given."""
+        if channel_axis not in (0, -1):
+            raise ValueError("channel_axis: 0 or -1")
+        last = self.channels > 1 and channel_axis == -1
+        img = self._img(np.moveaxis(np.asarray(image), -1, 0) if last else image)
+        out = np.empty(self.image_shape, dtype=out_dtype)
         st = C.PmStats()
         rc = C.check(self._L.mad_pm_run(self._ctx, img.ctypes.data_as(ctypes.c_void_p),
                                         mad_dtype(img.dtype), out.ctypes.data_as(ctypes.c_void_p),
@@ -124,6 +140,10 @@ class _Context:
         self.contrast_used = st.contrast_used
         if self.quantile:
             stats["contrast_used"] = st.contrast_used
+        if self.channels > 1:
+            stats["channels"] = self.channels
+        if last:
+            out = np.ascontiguousarray(np.moveaxis(out, 0, -1))
         return out, stats
 
     def tensor(self, image, with_diffusivity=False):
@@ -139,9 +159,10 @@ class _Context:
         return (T, g) if with_diffusivity else T
 
     def gradient(self, image):
-        """The gradient at the noise scale: (3, z, y, x) (gx, gy, gz) or (2, y, x) (gx, gy)."""
+        """The gradient at the noise scale: (3, z, y, x) (gx, gy, gz) or (2, y, x) (gx, gy);
+        channels > 1: (C, dim) + shape."""
         img = self._img(image)
-        G = np.empty((self.DIM,) + self.shape)
+        G = np.empty((() if self.channels == 1 else (self.channels,)) + (self.DIM,) + self.shape)
         self._check(self._L.mad_pm_gradient(
             self._ctx, img.ctypes.data_as(ctypes.c_void_p), mad_dtype(img.dtype),
             G.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
@@ -198,6 +219,7 @@ class PeronaMalikDiffusionImageFilter:
                        contrast_quantile=None)
         self._contrast_used = None
         self._input = None
+        self._channel_axis = None
         self._output = None
         self.stats = None
 
@@ -233,8 +255,13 @@ class PeronaMalikDiffusionImageFilter:
     SetConductanceParameter = SetContrast
     SetNumberOfIterations = SetIterations
 
-    def SetInput(self, image):
+    def SetInput(self, image, channel_axis=None):
+        """channel_axis (0 or -1): a vector-valued image; its array carries one axis more than
+        its spacing, the channels, and the output keeps that layout."""
+        if channel_axis not in (None, 0, -1):
+            raise ValueError("channel_axis: None, 0 or -1")
         self._input = image if isinstance(image, Image) else Image(image)
+        self._channel_axis = channel_axis
 
     def GetOutput(self):
         return self._output
@@ -247,11 +274,19 @@ class PeronaMalikDiffusionImageFilter:
             raise RuntimeError("SetInput must be called before Update")
         img = self._input
         out_dtype = self._output_dtype or img.array.dtype
-        ctx = PM2D if img.dim == 2 else PM
-        v = ctx(img.array.shape, img.spacing, smoother=self._smoother.smoother_id,
-                precision=self._precision, device=self._device, **self._p)
+        ax = self._channel_axis
+        if ax is None:
+            shape, channels, dim = img.array.shape, 1, img.dim
+        else:
+            shape = img.array.shape[1:] if ax == 0 else img.array.shape[:-1]
+            channels, dim = img.array.shape[ax], img.array.ndim - 1
+            if len(img.spacing) != dim:
+                raise ValueError("with channel_axis the array carries one axis more than the spacing")
+        ctx = PM2D if dim == 2 else PM
+        v = ctx(shape, img.spacing, smoother=self._smoother.smoother_id,
+                precision=self._precision, device=self._device, channels=channels, **self._p)
         try:
-            out, stats = v.run(img.array, out_dtype=out_dtype)
+            out, stats = v.run(img.array, out_dtype=out_dtype, channel_axis=ax or 0)
         finally:
             v.close()
         self.stats = stats

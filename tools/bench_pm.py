@@ -4,6 +4,7 @@ measured in the same run on bench_ved.py's synthetic tube phantom.
     python tools/bench_pm.py [--dim 3] [--size 256] [--reps 10] [--fp64] [--md FILE]
     python tools/bench_pm.py --dim 2 [--size 8192] ...
     python tools/bench_pm.py --quantile 0.9 [--image constant] ...
+    python tools/bench_pm.py --channels 3 [--dim 2] ...   (bench_channels: joint against C scalar)
 
 --quantile Q adds a third context in the same alternation, Perona-Malik with its contrast taken
 from the Q-quantile of the gradient magnitudes (include/mad_pm.h "Contrast from a quantile"), and
@@ -48,6 +49,66 @@ def summary(runs):
     return best, times[len(times) // 2], [round(r["tensor_ms"], 4) for r in runs]
 
 
+def vector_bytes(dim, C, fp64):
+    """(joint, C scalar generations), algorithmic bytes per voxel / pixel."""
+    if dim == 2:
+        return 8 * C + 24, 32 * C
+    z, y, x = pm_pass_bytes(fp64)
+    return (z + y) * C + (x - 48) * C + 48, (z + y + x) * C
+
+
+def bench_channels(a, M, img):
+    """--channels C: the joint generation of a C-channel image (include/mad_pm.h "Vector-valued
+    images") against C scalar generations, and a whole run against C scalar runs, alternating in
+    this process.  Channel c is the phantom rolled by 3 c along x plus 10 c, so the channels' edges
+    differ.  Times are the stats' HIP-event times; a scalar figure is the sum over the channels."""
+    dim, C = a.dim, a.channels
+    S = img.shape[0]
+    shape, sp = (S,) * dim, (1.0,) * dim
+    kw = dict(noise_scale=0.5, contrast=5.0, exponent=2.0, alpha=0.01, time_step=0.1, diffusion_iterations=1,
+              precision=M.FP64 if a.fp64 else M.FP32, diffusivity=a.diffusivity)
+    cls = M.PM if dim == 3 else M.PM2D
+    chans = np.stack([np.roll(img, 3 * c, axis=-1) + 10.0 * c for c in range(C)])
+    vec, one = cls(shape, sp, channels=C, **kw), cls(shape, sp, **kw)
+    vec.run(chans, out_dtype=np.float32)
+    one.run(chans[0], out_dtype=np.float32)
+    joint, split = [], []
+    for _ in range(a.reps):
+        joint.append(vec.run(chans, out_dtype=np.float32)[1])
+        per = [one.run(chans[c], out_dtype=np.float32)[1] for c in range(C)]
+        split.append({k: sum(p[k] for p in per) for k in ("tensor_ms", "diffusion_ms", "total_cycles")})
+    vec.close()
+    one.close()
+    bj, bs = min(joint, key=lambda r: r["tensor_ms"]), min(split, key=lambda r: r["tensor_ms"])
+    med = lambda runs, k: sorted(r[k] for r in runs)[len(runs) // 2]
+    Bj, Bs = vector_bytes(dim, C, a.fp64)
+    res = {"workload": f"{S}^{dim} tube phantom, {C} channels, sigma 0.5, K 5, {a.diffusivity}, 1 iteration, "
+                       "1 diffusion step of 0.1", "precision": "fp64" if a.fp64 else "fp32", "channels": C,
+           "joint": {"tensor_ms": round(bj["tensor_ms"], 4), "tensor_ms_median": round(med(joint, "tensor_ms"), 4),
+                     "diffusion_ms": round(bj["diffusion_ms"], 3), "cycles": bj["total_cycles"], "bytes": Bj,
+                     "pass_ms": [round(t, 4) for t in bj["pass_ms"]]},
+           "scalar_x_C": {"tensor_ms": round(bs["tensor_ms"], 4), "tensor_ms_median": round(med(split, "tensor_ms"), 4),
+                          "diffusion_ms": round(bs["diffusion_ms"], 3), "cycles": bs["total_cycles"], "bytes": Bs},
+           "tensor_ratio": round(bj["tensor_ms"] / bs["tensor_ms"], 3), "tensor_ratio_predicted": round(Bj / Bs, 3),
+           "run_ratio": round((med(joint, "tensor_ms") + med(joint, "diffusion_ms")) /
+                              (med(split, "tensor_ms") + med(split, "diffusion_ms")), 3)}
+    print(json.dumps(res), flush=True)
+    if a.md:
+        unit = "voxel" if dim == 3 else "pixel"
+        with open(a.md, "a") as f:
+            f.write(f"\n## {S}^{dim} {res['precision']}, {C} channels\n\n`python tools/bench_pm.py --dim {dim} --size {S} "
+                    f"--channels {C} --reps {a.reps}{' --fp64' if a.fp64 else ''}` on one MI355X; best of {a.reps} by "
+                    "tensor time (median beside it), the two alternating in one process.\n\n"
+                    f"| | tensor ms (best) | median | B/{unit} (algorithmic) | diffusion ms | cycles |\n|---|---|---|---|---|---|\n")
+            for label, k in (("joint generation", "joint"), (f"{C} scalar generations", "scalar_x_C")):
+                r = res[k]
+                f.write(f"| {label} | {r['tensor_ms']:.4f} | {r['tensor_ms_median']:.4f} | {r['bytes']} | "
+                        f"{r['diffusion_ms']} | {r['cycles']} |\n")
+            f.write(f"\nTensor time joint / scalar: {res['tensor_ratio']:.2f} (the byte counts alone predict "
+                    f"{res['tensor_ratio_predicted']:.2f}); whole run (tensor + diffusion, medians): "
+                    f"{res['run_ratio']:.2f}.\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dim", type=int, default=3, choices=(2, 3))
@@ -58,6 +119,8 @@ def main():
     ap.add_argument("--quantile", type=float, default=None, help="also time quantile mode at this q")
     ap.add_argument("--image", default="phantom", choices=("phantom", "constant"))
     ap.add_argument("--md", default=None, help="also write the result as a markdown file")
+    ap.add_argument("--channels", type=int, default=None,
+                    help="time the joint generation of a C-channel image against C scalar ones (--md appends)")
     a = ap.parse_args()
     import multigridanisotropicdiffusion_amd as M
     dim = a.dim
@@ -69,6 +132,8 @@ def main():
         img = bench_ced.phantom_slice(S)
     if a.image == "constant":
         img = np.full_like(img, 100.0)
+    if a.channels is not None:
+        return bench_channels(a, M, img)
     shape, sp = (S,) * dim, (1.0,) * dim
     common = dict(noise_scale=0.5, contrast=5.0, exponent=2.0, alpha=0.01, time_step=0.1,
                   diffusion_iterations=1, precision=M.FP64 if a.fp64 else M.FP32)
